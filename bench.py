@@ -11,6 +11,12 @@ row (the batched path-length traversal kernel). The headline config is
 BASELINE.json's: Standard IF, 1000 trees, 256-sample bags, 100M rows x 32
 features bf16 per GPU (weak scaling), synthetic Gaussian-mixture anomalies
 with random seeds. Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, print. ``--full`` adds the AUROC check of the last step's scores
+(``config.auroc``; null without it). ``--dump-outputs DIR`` writes the last
+timed step's outputs as ``DIR/<name>.npy``; data and per-step seeds are
+fixed by the arguments, so two builds can be compared output for output.
 """
 
 import argparse
@@ -96,6 +102,46 @@ def auroc_torch(y: torch.Tensor, scores: torch.Tensor) -> float:
     )
 
 
+DUMP_ARRAY_BYTES = 6 * 1024 * 1024  # per file; <= 9 files, so < 64 MB in all
+
+
+def _dump_sample_index(n: int, itemsize: int):
+    """Fixed, seeded (sorted) flat sample for an output too large to write
+    whole; None when all n elements fit."""
+    keep = DUMP_ARRAY_BYTES // itemsize
+    if n <= keep:
+        return None
+    return np.sort(np.random.RandomState(20240).randint(0, n, size=keep))
+
+
+def dump_outputs(out_dir: str, model, scores: torch.Tensor) -> None:
+    """Write what the last timed step handed back — the per-row scores and
+    the trained forest's arrays — as float32/float64 .npy files. Arrays
+    over DUMP_ARRAY_BYTES are written as the same seeded sample every run,
+    so two builds given the same arguments compare file for file."""
+    import dataclasses
+
+    os.makedirs(out_dir, exist_ok=True)
+
+    idx = _dump_sample_index(scores.numel(), 4)
+    flat = scores.reshape(-1)
+    if idx is not None:
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(os.path.join(out_dir, "scores.npy"),
+            flat.float().cpu().numpy())
+
+    for f in dataclasses.fields(model.forest):
+        arr = getattr(model.forest, f.name)
+        if not isinstance(arr, np.ndarray):
+            continue
+        # float32 stays float32; integers and doubles go to float64 (exact)
+        out_dtype = np.float32 if arr.dtype == np.float32 else np.float64
+        idx = _dump_sample_index(arr.size, np.dtype(out_dtype).itemsize)
+        out = arr if idx is None else arr.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"forest_{f.name}.npy"),
+                np.ascontiguousarray(out, dtype=out_dtype))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -113,7 +159,17 @@ def main():
                     help="after timing, rank 0 exports the trained model's "
                          "ONNX graph here (config #5's export leg; "
                          "standard IF only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after timing, rank 0 writes what the last timed "
+                         "step returned (scores + forest arrays) as "
+                         "DIR/<name>.npy, float32/float64, <= 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks the headline figure does not "
+                         "need (AUROC of the last step's scores on the "
+                         "planted anomalies)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_self_launch(args.gpus))
@@ -190,9 +246,15 @@ def main():
     ms_per_step = elapsed / args.steps * 1000.0
     rows_per_sec = rows_total * args.steps / elapsed
 
-    # quality (outside the timed region): AUROC on this rank's shard
-    sample = min(rows, 10_000_000)
-    measured_auroc = auroc_torch(y[:sample], scores[:sample])
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, scores)
+
+    # quality (outside the timed region, --full only): AUROC on this
+    # rank's shard
+    measured_auroc = None
+    if args.full:
+        sample = min(rows, 10_000_000)
+        measured_auroc = round(auroc_torch(y[:sample], scores[:sample]), 4)
 
     if rank == 0 and args.export_onnx and not args.extended:
         from isolation_forest_amd.onnx import IsolationForestConverter
@@ -224,7 +286,7 @@ def main():
                 "parallelism": f"row-sharded dp{world_size} + tree-sharded build",
                 "world_size": world_size,
                 "contamination": args.contamination,
-                "auroc": round(measured_auroc, 4),
+                "auroc": measured_auroc,
                 "device": device.split(":")[0],
             },
         }
