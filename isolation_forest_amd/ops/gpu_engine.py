@@ -19,7 +19,8 @@ width and dtype (score_extended_forest):
 * nnz <= 5 uniform -> sparse v2 (bitwise strict j-order),
 * densifiable (nnz == d or nnz >= 6): bf16 rows -> dense v3 (packed
   bf16 weights, d <= 128), f32 rows -> dense v2 (d <= 64) — tolerance
-  contracts per PARITY.md,
+  contracts per PARITY.md; a batch with a non-finite cell and nnz < d
+  skips the densified route (0 * inf = NaN) for the general kernel,
 * otherwise (wide d, ragged widths, LDS overflow) -> the general
   strict-order kernel; forests past the packed 15-bit-node/12-bit-
   feature caps use the wide int4 kernels.
@@ -923,7 +924,14 @@ def score_extended_forest(model, X: torch.Tensor, finalize: bool = True) -> torc
                 X.contiguous(), aos, extra["values"], extra["hidx"],
                 extra["hw"], ncount, extra["height"], c, finalize,
             )
-    if d <= 128 and (nnz == d or nnz >= 6):
+    # densified hyperplanes (nnz < d) carry weight 0 on unselected
+    # coordinates: 0 * inf/NaN = NaN would route a row right where the
+    # oracle never reads that coordinate, so a batch with a non-finite cell
+    # takes the general strict-order kernel below (bitwise). nnz == d has
+    # no zero-padded real column and stays unguarded: the dense bindings
+    # rescore its non-finite rows in strict order themselves.
+    if d <= 128 and (nnz == d or (
+            nnz >= 6 and bool(torch.isfinite(X).all().item()))):
         if d <= 8:
             D = 8
         elif d <= 16:

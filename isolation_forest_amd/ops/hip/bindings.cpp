@@ -87,6 +87,11 @@ void launch_score_extended_dense_v3(int D, bool rpt2, const void* X,
                                     size_t lds, int blocks,
                                     hipStream_t stream);
 
+void launch_score_extended_dense_nonfinite_rows(
+    bool bf16, bool packed_w, const void* X, const void* nodes,
+    const float* values, const void* wts, float* out, int64_t N, int32_t d,
+    int32_t D, int32_t T, int32_t max_nodes, int32_t height_limit, float fT,
+    float c_norm, int finalize, int blocks, hipStream_t stream);
 void launch_score_forest_wide(bool bf16, const void* X, const void* nodes,
                               float* out, int64_t N, int32_t d, int32_t T,
                               int64_t max_nodes, int32_t height_limit,
@@ -430,6 +435,13 @@ torch::Tensor score_extended_dense_v2(torch::Tensor X,
       ncount.data_ptr<int32_t>(), out.data_ptr<float>(), N, (int32_t)d,
       (int32_t)T, (int32_t)max_nodes, (int32_t)height_limit, (float)T,
       (float)c_norm, finalize ? 1 : 0, lds, blocks, current_stream());
+  // rows with an inf/NaN cell: strict-order rescoring (see the kernel)
+  ifa::launch_score_extended_dense_nonfinite_rows(
+      is_bf16(X), false, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
+      values.data_ptr<float>(), hw.data_ptr<float>(), out.data_ptr<float>(),
+      N, (int32_t)d, (int32_t)D, (int32_t)T, (int32_t)max_nodes,
+      (int32_t)height_limit, (float)T, (float)c_norm, finalize ? 1 : 0,
+      (int)std::min<int64_t>((N + 255) / 256, 8192), current_stream());
   return out;
 }
 
@@ -478,6 +490,14 @@ torch::Tensor score_extended_dense_v3(torch::Tensor X,
       ncount.data_ptr<int32_t>(), out.data_ptr<float>(), N, (int32_t)d,
       (int32_t)T, (int32_t)max_nodes, (int32_t)height_limit, (float)T,
       (float)c_norm, finalize ? 1 : 0, lds, blocks, current_stream());
+  // rows with an inf/NaN cell: strict-order rescoring (see the kernel)
+  ifa::launch_score_extended_dense_nonfinite_rows(
+      true, true, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
+      values.data_ptr<float>(), hwp.data_ptr<int32_t>(),
+      out.data_ptr<float>(), N, (int32_t)d, (int32_t)D, (int32_t)T,
+      (int32_t)max_nodes, (int32_t)height_limit, (float)T, (float)c_norm,
+      finalize ? 1 : 0, (int)std::min<int64_t>((N + 255) / 256, 8192),
+      current_stream());
   return out;
 }
 

@@ -26,6 +26,9 @@
 //    128: weights staged as RNE-rounded PACKED bf16 (half the LDS bytes
 //    of v2 — its measured bound), rows as packed-bf16 register pairs,
 //    dot on v_dot2c_f32_bf16. Contract: PARITY.md "Numeric contracts".
+//  * score_extended_dense_nonfinite_rows — runs after dense v2/v3: rows
+//    with an inf/NaN cell are rescored in strict j-order (bitwise), since
+//    overflowing partial sums make their branch depend on the dot order.
 //  * score_extended_sparse_v2     — K7 small-nnz path (templated NNZ<=5):
 //    same fixed-trip structure, strict oracle j-order dot (bitwise).
 //    extensionLevel-0 forests do NOT use it: they are packed onto
@@ -1106,6 +1109,93 @@ score_extended_dense_v3(
 }
 
 // ---------------------------------------------------------------------------
+// dense v2/v3 companion: rows holding an inf/NaN cell, rescored in the
+// oracle's strict j-order.
+//
+// With nnz == d such a row's dot is inf or NaN in every summation order,
+// but WHICH of the two depends on the order once finite partial sums
+// overflow (+-3e38 cells): -inf + (a + b -> +inf) = NaN, while
+// ((-inf + a) + b) = -inf, and NaN < offset is false where -inf < offset is
+// true. The 4-chain kernels above therefore cannot promise the oracle's
+// branch on these rows. This pass runs after them on the same stream: a
+// coalesced scan flags the rows of each 256-row tile that hold a
+// non-finite cell, and only those rows walk every tree again with the
+// strict mul/add dot (weights and nodes from global memory — a correctness
+// path) and overwrite their output. Clean rows are left untouched, so the
+// fast kernels keep their registers and occupancy. PACKED_W = v3's packed
+// bf16 weight pairs, else v2's padded f32 weights. Bitwise vs
+// cpu_engine.path_lengths_extended for nnz == d.
+// ---------------------------------------------------------------------------
+
+__device__ __forceinline__ bool nonfinite_bits(uint16_t b) {
+  return (b & 0x7F80u) == 0x7F80u;
+}
+__device__ __forceinline__ bool nonfinite_bits(uint32_t b) {
+  return (b & 0x7F800000u) == 0x7F800000u;
+}
+
+template <typename KT, bool PACKED_W>
+__global__ void __launch_bounds__(256) score_extended_dense_nonfinite_rows(
+    const KT* __restrict__ X,           // raw bits [N][d]
+    const int2* __restrict__ nodes,     // [T][max_nodes] {right<<12, offset/-inf}
+    const float* __restrict__ values,   // [T][max_nodes] leaf value+depth
+    const void* __restrict__ wts,       // f32 [T][max_nodes][D] or packed
+                                        // bf16 pairs u32 [T][max_nodes][D/2]
+    float* __restrict__ out, int64_t N, int32_t d, int32_t D, int32_t T,
+    int32_t max_nodes, int32_t height_limit, float fT, float c_norm,
+    int32_t finalize) {
+  __shared__ int flagged[256];
+  const int tid = threadIdx.x;
+  for (int64_t block_row0 = (int64_t)blockIdx.x * 256; block_row0 < N;
+       block_row0 += (int64_t)gridDim.x * 256) {
+    const int rows_here = (int)min((int64_t)256, N - block_row0);
+    __syncthreads();  // previous iteration's flag readers done
+    flagged[tid] = 0;
+    __syncthreads();
+    const int total = rows_here * d;
+    for (int g = tid; g < total; g += 256)
+      if (nonfinite_bits(X[block_row0 * d + g]))
+        flagged[g / d] = 1;  // every writer stores the same value
+    __syncthreads();
+    if (tid >= rows_here || !flagged[tid]) continue;
+
+    const int64_t my_row = block_row0 + tid;
+    float psum = 0.f;
+    for (int t = 0; t < T; ++t) {
+      const int64_t tbase = (int64_t)t * max_nodes;
+      int cur = 0;
+      for (int it = 0; it < height_limit; ++it) {
+        const int2 nd = nodes[tbase + cur];
+        const int right = pn_right(nd.x);
+        if (right == cur) break;  // leaf self-loop
+        float dot = 0.f;
+        for (int j = 0; j < d; ++j) {  // oracle j-order
+          float w;
+          if (PACKED_W) {
+            const uint32_t pw =
+                ((const uint32_t*)wts)[(tbase + cur) * (D / 2) + (j >> 1)];
+            w = __uint_as_float((j & 1) ? (pw & 0xFFFF0000u) : (pw << 16));
+          } else {
+            w = ((const float*)wts)[(tbase + cur) * D + j];
+          }
+          dot = __fadd_rn(dot,
+                          __fmul_rn(w, load_row_f32<KT>(X, my_row * d + j)));
+        }
+        cur = (dot < __int_as_float(nd.y)) ? cur + 1 : right;
+      }
+      psum = __fadd_rn(psum, values[tbase + cur]);
+    }
+    if (finalize) {
+      const float mean32 = (float)((double)psum / (double)fT);
+      const double ratio = (double)mean32 / (double)c_norm;
+      out[my_row] = (float)exp2(-ratio);
+    } else {
+      out[my_row] = psum;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // extended scoring, sparse fast path v2 (nnz <= 5, templated):
 // same node/value packing as the dense v2 kernel (self-looping leaves with
 // offset -inf and zero weights => fixed-trip walks), rows staged native in
@@ -1634,6 +1724,24 @@ void launch_score_extended_dense_v3(int D, bool rpt2, const void* X,
   else if (D == 64) LSD3(64, 1);
   else LSD3(128, 1);
 #undef LSD3
+}
+
+void launch_score_extended_dense_nonfinite_rows(
+    bool bf16, bool packed_w, const void* X, const void* nodes,
+    const float* values, const void* wts, float* out, int64_t N, int32_t d,
+    int32_t D, int32_t T, int32_t max_nodes, int32_t height_limit, float fT,
+    float c_norm, int finalize, int blocks, hipStream_t stream) {
+#define LNF(KT, PW)                                                           \
+  hipLaunchKernelGGL((score_extended_dense_nonfinite_rows<KT, PW>),           \
+                     dim3(blocks), dim3(256), 0, stream, (const KT*)X,        \
+                     (const int2*)nodes, values, wts, out, N, d, D, T,        \
+                     max_nodes, height_limit, fT, c_norm, finalize)
+  if (bf16) {
+    if (packed_w) LNF(uint16_t, true); else LNF(uint16_t, false);
+  } else {
+    LNF(uint32_t, false);  // v3 (packed weights) takes bf16 rows only
+  }
+#undef LNF
 }
 
 void launch_score_extended_sparse_v2(bool bf16, int nnz, const void* X,
