@@ -659,3 +659,220 @@ def score_forest(forest: Forest, X: np.ndarray) -> np.ndarray:
 def score_extended_forest(fr: ExtendedForest, X: np.ndarray) -> np.ndarray:
     ps = path_lengths_extended(fr, X)
     return scores_from_path_sums(ps, fr.num_trees, fr.num_samples)
+
+
+# ---------------------------------------------------------------------------
+# Per-feature score attribution (path-length decomposition, Saabas style).
+# No analogue in the reference; the contract is docs/DESIGN.md §8. These
+# functions are the oracle for the explain_* HIP kernels (bitwise).
+# ---------------------------------------------------------------------------
+
+
+def _leaf_path_values(forest) -> np.ndarray:
+    """f32(depth) + f32(value) per node — the leaf term of the v4 pack and
+    _path_lengths_fast (only meaningful at leaves)."""
+    from ..ops.gpu_engine import _node_depths
+
+    depth = _node_depths(forest.feature, forest.right)
+    return (depth.astype(np.float32)
+            + forest.value.astype(np.float32)).astype(np.float32)
+
+
+def node_expectations(forest) -> Tuple[np.ndarray, np.ndarray]:
+    """Expected path length E[v] (float64) of a training row below every
+    node, and the instance count n[v] (int64) it is weighted by.
+
+    Leaf: E = f64(f32(depth) + f32(value)), n = num_instances. Internal:
+    n = n_l + n_r, E = (n_l*E_l + n_r*E_r)/n, or the plain mean of the two
+    children when n == 0 (EIF zero-instance leaves). Internal nodes carry
+    num_instances = -1, so counts always come from the leaves. One reverse
+    pre-order sweep suffices because left = id+1 and right > id. Works on
+    Forest and ExtendedForest; pad nodes stay 0."""
+    feat = forest.feature
+    T, mn = feat.shape
+    leaf = feat == Forest.LEAF
+    E = np.where(leaf, _leaf_path_values(forest).astype(np.float64), 0.0)
+    n = np.where(leaf, forest.num_instances.astype(np.int64), 0)
+    right = forest.right.astype(np.int64)
+    for v in range(mn - 2, -1, -1):
+        ts = np.nonzero(feat[:, v] >= 0)[0]
+        if not len(ts):
+            continue
+        r = right[ts, v]
+        nl, nr = n[ts, v + 1], n[ts, r]
+        el, er = E[ts, v + 1], E[ts, r]
+        nv = nl + nr
+        safe = np.where(nv > 0, nv, 1).astype(np.float64)
+        E[ts, v] = np.where(nv > 0, (nl * el + nr * er) / safe,
+                            (el + er) / 2.0)
+        n[ts, v] = nv
+    return E, n
+
+
+def edge_deltas(forest, E: np.ndarray = None):
+    """(delta_left, delta_right) float64 [T, mn]: E[child] - E[v] for the
+    two edges leaving every internal node, 0 at leaves and pads. Callers
+    round ONCE to float32 (after the EIF share multiply, if any)."""
+    if E is None:
+        E, _ = node_expectations(forest)
+    T, mn = forest.feature.shape
+    internal = forest.feature >= 0
+    ti = np.broadcast_to(np.arange(T, dtype=np.int64)[:, None], (T, mn))
+    ids = np.broadcast_to(np.arange(mn, dtype=np.int64)[None, :], (T, mn))
+    lid = np.where(internal, ids + 1, ids)
+    rid = np.where(internal, forest.right.astype(np.int64), ids)
+    dl = np.where(internal, E[ti, lid] - E, 0.0)
+    dr = np.where(internal, E[ti, rid] - E, 0.0)
+    return dl, dr
+
+
+def explain_tables(forest):
+    """Cached per-forest attribution tables (forests are immutable):
+    ``bias`` = f32(mean_t E[root_t]) and float32 edge deltas. Standard:
+    ``dl``/``dr`` [T, mn]. Extended: [T, mn, nnz] — the node's delta shared
+    over its k = feature[t, v] hyperplane coordinates in proportion to
+    w_j^2 (float64 from the f32 weights; equal shares when the sum is 0 or
+    non-finite), each share rounded once; slots j >= k hold +0.0.
+
+    The cache lives on the forest object and assumes what the models'
+    device pack caches assume too: a forest's arrays are not edited once it
+    has been scored or explained (core/forest.py). leaf_values_from_counts()
+    drops it; any other in-place edit must call
+    forest.invalidate_derived()."""
+    tabs = getattr(forest, "_explain_tables", None)
+    if tabs is not None:
+        return tabs
+    E, _ = node_expectations(forest)
+    dl64, dr64 = edge_deltas(forest, E)
+    bias = (np.float32(E[:, 0].mean()) if forest.num_trees
+            else np.float32(0.0))
+    if isinstance(forest, ExtendedForest):
+        nnz = forest.nnz
+        k = np.where(forest.feature >= 0, forest.feature, 0).astype(np.int64)
+        used = np.arange(nnz, dtype=np.int64)[None, None, :] < k[:, :, None]
+        w = forest.hyper_w.astype(np.float64)
+        sq = np.where(used, w * w, 0.0)
+        tot = np.zeros(k.shape, dtype=np.float64)
+        with np.errstate(over="ignore", invalid="ignore"):
+            for j in range(nnz):  # ascending j, like every other EIF sum
+                tot = tot + sq[:, :, j]
+        ok = np.isfinite(tot) & (tot > 0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            share = np.where(
+                ok[:, :, None], sq / np.where(ok, tot, 1.0)[:, :, None],
+                1.0 / np.maximum(k, 1)[:, :, None].astype(np.float64))
+        share = np.where(used, share, 0.0)
+        dl = (dl64[:, :, None] * share).astype(np.float32)
+        dr = (dr64[:, :, None] * share).astype(np.float32)
+        dl[~used] = 0.0
+        dr[~used] = 0.0
+    else:
+        dl = dl64.astype(np.float32)
+        dr = dr64.astype(np.float32)
+    tabs = {"bias": bias, "dl": np.ascontiguousarray(dl),
+            "dr": np.ascontiguousarray(dr)}
+    forest._explain_tables = tabs
+    return tabs
+
+
+def expected_path_length(forest) -> np.float32:
+    """The attribution bias: f32(mean over trees of E[root])."""
+    return explain_tables(forest)["bias"]
+
+
+def _finalize_contributions(acc: np.ndarray, num_trees: int, finalize: bool):
+    if not finalize:
+        return acc
+    return (acc / np.float32(num_trees)).astype(np.float32)
+
+
+def feature_contributions(forest: Forest, X: np.ndarray,
+                          finalize: bool = True) -> np.ndarray:
+    """Per-feature path-length contributions, float32 [N, d].
+
+    The fixed-trip walk of _path_lengths_fast with one more thing carried
+    along: a row visiting internal node v (split feature f) adds the taken
+    edge's f32 delta to acc[row, f]. acc is float32, added in tree order
+    and root-to-leaf within a tree (the explain_forest kernel's order).
+    finalize=True returns f32(acc / f32(T)); with expected_path_length the
+    row sums reproduce the mean path length. Negative = the feature
+    shortened the path (more anomalous)."""
+    X = np.asarray(X)
+    N, d = X.shape
+    T, mn = forest.feature.shape
+    feat = forest.feature
+    internal = feat >= 0
+    live = internal | (feat == Forest.LEAF)
+    right = forest.right.astype(np.int64)
+    v64_all = (forest.value64 if getattr(forest, "value64", None) is not None
+               else forest.value.astype(np.float64))
+    tabs = explain_tables(forest)
+    from ..ops.gpu_engine import _node_depths
+
+    depth = _node_depths(feat, forest.right)
+    max_depth = int(depth[live].max()) if live.any() else 0
+    ids = np.broadcast_to(np.arange(mn, dtype=np.int64)[None, :], (T, mn))
+    fcol = np.where(internal, feat.astype(np.int64), d)
+    nxt_r = np.where(internal, right, ids)
+    thr = np.where(internal, v64_all, -np.inf)
+
+    Xa = np.concatenate([X, np.full((N, 1), np.inf, dtype=X.dtype)], axis=1)
+    rows = np.arange(N)
+    acc = np.zeros((N, d + 1), dtype=np.float32)  # column d: leaf self-loops
+    for t in range(T):
+        cur = np.zeros(N, dtype=np.int64)
+        f_t, r_t, thr_t = fcol[t], nxt_r[t], thr[t]
+        dl_t, dr_t = tabs["dl"][t], tabs["dr"][t]
+        for _ in range(max_depth):
+            f = f_t[cur]
+            go_left = Xa[rows, f] < thr_t[cur]
+            delta = np.where(go_left, dl_t[cur], dr_t[cur])
+            acc[rows, f] = acc[rows, f] + delta  # one f32 add per row
+            cur = np.where(go_left, cur + 1, r_t[cur])
+    return _finalize_contributions(
+        np.ascontiguousarray(acc[:, :d]), T, finalize)
+
+
+def feature_contributions_extended(fr: ExtendedForest, X: np.ndarray,
+                                   finalize: bool = True) -> np.ndarray:
+    """EIF contributions, float32 [N, d]: the path_lengths_extended walk
+    (strict j-order f32 dot < value) adding, per visited node, the taken
+    edge's per-coordinate shares to acc[row, hyper_idx[j]] in ascending j
+    over the node's k coordinates."""
+    X = np.asarray(X)
+    N, d = X.shape
+    nnz = fr.nnz
+    tabs = explain_tables(fr)
+    acc = np.zeros((N, d), dtype=np.float32)
+    for t in range(fr.num_trees):
+        feat = fr.feature[t]
+        val = fr.value[t]
+        right = fr.right[t]
+        hidx = fr.hyper_idx[t]
+        hw = fr.hyper_w[t]
+        dl_t, dr_t = tabs["dl"][t], tabs["dr"][t]
+        cur = np.zeros(N, dtype=np.int64)
+        active = feat[cur] >= 0
+        while active.any():
+            rows = np.nonzero(active)[0]
+            nodes = cur[rows]
+            dot = np.zeros(len(rows), dtype=np.float32)
+            with np.errstate(over="ignore", invalid="ignore"):
+                for j in range(nnz):  # inf/NaN cells: NaN compares false
+                    c = hidx[nodes, j]
+                    prod = (hw[nodes, j] * X[rows, c]).astype(np.float32)
+                    dot = (dot + prod).astype(np.float32)
+            go_left = dot < val[nodes]
+            k = feat[nodes]
+            for j in range(nnz):
+                m = j < k
+                rj, nj = rows[m], nodes[m]
+                c = hidx[nj, j]
+                delta = np.where(go_left[m], dl_t[nj, j], dr_t[nj, j])
+                acc[rj, c] = acc[rj, c] + delta
+            nxt = np.where(go_left, nodes + 1, right[nodes])
+            cur[rows] = nxt
+            active2 = np.zeros(N, dtype=bool)
+            active2[rows] = feat[nxt] >= 0
+            active = active2
+    return _finalize_contributions(acc, fr.num_trees, finalize)

@@ -95,8 +95,17 @@ class Forest:
             self.subtree_depth(t, i + 1), self.subtree_depth(t, int(self.right[t, i]))
         )
 
+    def invalidate_derived(self):
+        """Drop tables derived from the arrays (the attribution tables of
+        cpu_engine.explain_tables). A forest is treated as immutable once
+        it has been scored or explained: those caches, like a model's
+        device packs, are not keyed on the arrays' contents, so code that
+        edits the arrays in place afterwards must call this."""
+        self.__dict__.pop("_explain_tables", None)
+
     def leaf_values_from_counts(self):
         """(Re)compute leaf path-length terms from num_instances in place."""
+        self.invalidate_derived()
         leaf_mask = self.feature == Forest.LEAF
         counts = np.where(leaf_mask, self.num_instances, 0)
         self.value = np.where(
@@ -173,7 +182,12 @@ class ExtendedForest:
             self.subtree_depth(t, i + 1), self.subtree_depth(t, int(self.right[t, i]))
         )
 
+    def invalidate_derived(self):
+        """See Forest.invalidate_derived."""
+        self.__dict__.pop("_explain_tables", None)
+
     def leaf_values_from_counts(self):
+        self.invalidate_derived()
         leaf_mask = self.feature == ExtendedForest.LEAF
         counts = np.where(leaf_mask, self.num_instances, 0)
         self.value = np.where(

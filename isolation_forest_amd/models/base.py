@@ -127,6 +127,51 @@ class ModelBase:
             return np.zeros(scores.shape, dtype=np.float64)
         return (scores.astype(np.float64) >= self._threshold).astype(np.float64)
 
+    # -- per-feature attribution (docs/DESIGN.md §8) ---------------------
+    # Subclasses name their engine entry points; the forest kind is the
+    # only difference between the two models here.
+    _explain_cpu = None  # cpu_engine function (forest, X, finalize)
+    _explain_gpu = None  # gpu_engine function name (model, X, finalize)
+
+    def feature_contributions(self, X, finalize: bool = True) -> torch.Tensor:
+        """Per-feature path-length contributions, float32 [N, d] on X's
+        device. ``expected_path_length + contributions[i].sum()`` is row
+        i's mean path length; a NEGATIVE entry means the feature shortened
+        the path, i.e. made the row more anomalous. ``finalize=False``
+        returns the raw per-tree sums (not divided by the tree count)."""
+        self._check_scorable()
+        validate_feature_vector_size(self.forest.total_num_features, X.shape[1])
+        if isinstance(X, torch.Tensor) and X.is_cuda:
+            from ..ops import gpu_engine
+
+            return getattr(gpu_engine, self._explain_gpu)(self, X, finalize)
+        Xc = X.contiguous().float().numpy() if isinstance(X, torch.Tensor) else X
+        return torch.from_numpy(
+            type(self)._explain_cpu(self.forest, Xc, finalize))
+
+    @property
+    def expected_path_length(self) -> float:
+        """The attribution bias: the mean over trees of the expected path
+        length at the root (a model constant)."""
+        if self.__dict__.get("_expected_path_length") is None:
+            from ..core import cpu_engine
+
+            self._check_scorable()
+            self._expected_path_length = float(
+                cpu_engine.expected_path_length(self.forest))
+        return self._expected_path_length
+
+    def top_contributing_features(self, X, k: int):
+        """(indices int64 [N, k], values float32 [N, k]): the k most
+        negative contributions per row, most negative first."""
+        d = int(X.shape[1])
+        if not 1 <= int(k) <= d:
+            raise ValueError(f"k must be in [1, {d}], got {k}")
+        contrib = self.feature_contributions(X)
+        values, indices = torch.topk(contrib, int(k), dim=1, largest=False,
+                                     sorted=True)
+        return indices, values
+
 
 def fit_threshold(model, scores: torch.Tensor, params: Params, comm=None):
     """computeAndSetModelThreshold (SharedTrainLogic.scala:175-242)."""

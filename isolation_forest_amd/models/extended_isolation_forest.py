@@ -87,6 +87,9 @@ class ExtendedIsolationForest(IsolationForest):
 class ExtendedIsolationForestModel(ModelBase):
     _uid_prefix = "extended-isolation-forest"
 
+    _explain_cpu = staticmethod(cpu_engine.feature_contributions_extended)
+    _explain_gpu = "explain_extended_forest"
+
     def __init__(self, uid: str, forest: ExtendedForest, params: ExtendedParams):
         super().__init__(uid, params)
         self.forest = forest

@@ -205,6 +205,8 @@ class IsolationForestModel(ModelBase):
     (IsolationForestModel.scala:37-96)."""
 
     _uid_prefix = "isolation-forest"
+    _explain_cpu = staticmethod(cpu_engine.feature_contributions)
+    _explain_gpu = "explain_forest"
 
     def __init__(self, uid: str, forest: Forest, params: Params):
         super().__init__(uid, params)

@@ -339,6 +339,49 @@ def _nodes_packed_wide(forest, bf16: bool):
     return packed, max(max_depth, 1)
 
 
+def _nodes_packed_explain(forest, d_sentinel: int, bf16: bool):
+    """16-byte node records for explain_forest_kernel:
+    {feat | right<<12, integer key threshold, delta_left bits,
+    delta_right bits}. Threshold math is _nodes_packed_v4's; the f32 edge
+    deltas are cpu_engine.explain_tables' (shared with the CPU oracle, so
+    the kernel only has to reproduce the walk and the adds). Leaves and
+    pads self-loop with feat = d_sentinel, threshold 0 (the sentinel key
+    0xFFFFFFFF never compares below it) and both deltas +0.0.
+    Returns (packed int32 [T, mn, 4], max_depth)."""
+    from ..core.cpu_engine import explain_tables
+
+    T, mn = forest.feature.shape
+    if mn > 32767:
+        raise ValueError("forest too deep for the packed node format")
+    feat = forest.feature
+    if feat.max(initial=0) > 4094 or d_sentinel > 4094:
+        raise ValueError("GPU scoring supports at most 4095 features")
+    internal = feat >= 0
+    leaf = feat == Forest.LEAF
+    tabs = explain_tables(forest)
+    ids = np.broadcast_to(np.arange(mn, dtype=np.int32)[None, :], (T, mn))
+    w0 = np.where(
+        internal,
+        feat.astype(np.int32) | (forest.right.astype(np.int32) << 12),
+        np.int32(d_sentinel) | (ids << 12),
+    ).astype(np.int32)
+    w1 = np.zeros((T, mn), dtype=np.uint32)
+    if internal.any():
+        s = _split_thresholds32(forest)[internal]
+        w1[internal] = _bf16_threshold_keys(s) if bf16 else _key32(s)
+    packed = np.zeros((T, mn, 4), dtype=np.int32)
+    packed[..., 0] = w0
+    packed[..., 1] = w1.view(np.int32)
+    packed[..., 2] = np.where(internal, tabs["dl"], np.float32(0.0)).astype(
+        np.float32).view(np.int32)
+    packed[..., 3] = np.where(internal, tabs["dr"], np.float32(0.0)).astype(
+        np.float32).view(np.int32)
+    depth = _node_depths(feat, forest.right)
+    live = internal | leaf
+    max_depth = int(depth[live].max()) if live.any() else 0
+    return packed, max(max_depth, 1)
+
+
 def _eif_packed_wide(forest):
     """Wide int4 node records {is_leaf(-1)/0, right, value_bits, 0} for
     score_extended_wide (strict oracle j-order dot from global
@@ -782,6 +825,28 @@ def _device_forest(model, device, v4_key=None):
             aos = torch.from_numpy(packed).to(device)
             ncount = torch.from_numpy(ncount_np).to(device)
             extra["height"] = max_depth
+        elif isinstance(v4_key, tuple) and v4_key[0] == "explain":
+            packed, max_depth = _nodes_packed_explain(
+                forest, v4_key[1], v4_key[2])
+            aos = torch.from_numpy(packed).to(device)
+            ncount = torch.from_numpy(
+                np.ascontiguousarray(forest.node_count, dtype=np.int32)
+            ).to(device)
+            extra["height"] = max_depth
+        elif v4_key == "eif_explain":
+            from ..core.cpu_engine import explain_tables
+
+            tabs = explain_tables(forest)
+            aos = torch.from_numpy(_nodes_packed(forest)).to(device)
+            ncount = torch.from_numpy(
+                np.ascontiguousarray(forest.node_count, dtype=np.int32)
+            ).to(device)
+            extra["hidx"] = torch.from_numpy(
+                np.ascontiguousarray(forest.hyper_idx)).to(device)
+            extra["hw"] = torch.from_numpy(
+                np.ascontiguousarray(forest.hyper_w)).to(device)
+            extra["dl"] = torch.from_numpy(tabs["dl"]).to(device)
+            extra["dr"] = torch.from_numpy(tabs["dr"]).to(device)
         elif isinstance(v4_key, tuple) and v4_key[0] == "wide":
             packed, max_depth = _nodes_packed_wide(forest, v4_key[1])
             aos = torch.from_numpy(packed).to(device)
@@ -969,3 +1034,78 @@ def score_extended_forest(model, X: torch.Tensor, finalize: bool = True) -> torc
     return ext.score_extended_forest(
         X.contiguous(), aos, extra["hidx"], extra["hw"], ncount, c, finalize
     )
+
+
+# ---------------------------------------------------------------------------
+# per-feature attribution (docs/DESIGN.md §8)
+# ---------------------------------------------------------------------------
+
+
+def _explain_on_cpu(fn, forest, X: torch.Tensor, finalize: bool, why: str):
+    """Forests past the packed-record caps: CPU oracle, result moved to X's
+    device (a correctness path; there are no wide-record explain kernels)."""
+    import logging
+
+    logging.getLogger(__name__).warning(
+        "feature_contributions: %s; computing on the CPU oracle", why)
+    Xc = X.detach().float().cpu().contiguous().numpy()
+    return torch.from_numpy(fn(forest, Xc, finalize)).to(X.device)
+
+
+def _check_explain_input(X: torch.Tensor):
+    if X.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("feature_contributions expects float32 or bfloat16 "
+                         f"rows on the GPU, got {X.dtype}")
+
+
+def explain_forest(model, X: torch.Tensor, finalize: bool = True) -> torch.Tensor:
+    """Standard-forest contributions [N, d] float32 on X's device, bitwise
+    equal to cpu_engine.feature_contributions."""
+    from ..core import cpu_engine
+
+    forest = model.forest
+    d = int(X.shape[1])
+    _check_explain_input(X)
+    fmax = int(forest.feature.max(initial=-1))
+    if fmax >= d:
+        raise ValueError(
+            f"the forest splits on feature {fmax} but rows have {d} columns")
+    if not _packed_fits(forest, d):
+        return _explain_on_cpu(
+            cpu_engine.feature_contributions, forest, X, finalize,
+            "forest exceeds the packed node format (15-bit node ids, "
+            "12-bit feature ids)")
+    ext = load_extension()
+    bf16 = X.dtype == torch.bfloat16
+    aos, ncount, extra = _device_forest(
+        model, X.device, v4_key=("explain", d, bf16))
+    return ext.explain_forest(X.contiguous(), aos, ncount, extra["height"],
+                              finalize)
+
+
+def explain_extended_forest(model, X: torch.Tensor,
+                            finalize: bool = True) -> torch.Tensor:
+    """EIF contributions [N, d] float32 on X's device, bitwise equal to
+    cpu_engine.feature_contributions_extended at every extension level
+    (one strict-order kernel, no routing)."""
+    from ..core import cpu_engine
+
+    forest = model.forest
+    d = int(X.shape[1])
+    _check_explain_input(X)
+    internal = forest.feature >= 0
+    cmax = (int(forest.hyper_idx[internal].max(initial=-1))
+            if internal.any() else -1)
+    if cmax >= d:
+        raise ValueError(
+            f"the forest splits on feature {cmax} but rows have {d} columns")
+    if not _packed_fits(forest, d):
+        return _explain_on_cpu(
+            cpu_engine.feature_contributions_extended, forest, X, finalize,
+            "forest exceeds the packed node format (15-bit node ids, "
+            "12-bit hyperplane widths)")
+    ext = load_extension()
+    aos, ncount, extra = _device_forest(model, X.device, v4_key="eif_explain")
+    return ext.explain_extended_forest(
+        X.contiguous(), aos, extra["hidx"], extra["hw"], extra["dl"],
+        extra["dr"], finalize)

@@ -105,6 +105,21 @@ void launch_score_extended_wide(bool bf16, const void* X, const void* nodes,
                                 float c_norm, int finalize, int blocks,
                                 hipStream_t stream);
 
+void launch_explain_forest(bool bf16, int mode, int rpt, bool nodes_lds,
+                           const void* X, const void* nodes,
+                           const int32_t* ncount, float* out, int64_t N,
+                           int32_t d, int32_t dpad, int32_t astride,
+                           int32_t T, int32_t max_nodes, int32_t tps,
+                           int32_t height_limit, float fT, int finalize,
+                           size_t lds, int blocks, hipStream_t stream);
+
+void launch_explain_extended(bool bf16, const void* X, const void* nodes,
+                             const int32_t* hidx, const float* hw,
+                             const float* dl, const float* dr, float* out,
+                             int64_t N, int32_t d, int32_t T,
+                             int32_t max_nodes, int32_t nnz, float fT,
+                             int finalize, int blocks, hipStream_t stream);
+
 }  // namespace ifa
 
 namespace {
@@ -602,6 +617,164 @@ torch::Tensor score_extended_wide(torch::Tensor X, torch::Tensor nodes_wide,
   return out;
 }
 
+// Per-feature attribution, standard forests (explain_forest_kernel).
+// Returns the f32 [N, d] contribution matrix (raw sums when !finalize).
+torch::Tensor explain_forest(torch::Tensor X, torch::Tensor nodes_explain,
+                             torch::Tensor ncount, int64_t height_limit,
+                             bool finalize) {
+  CHECK_CUDA(X);
+  CHECK_CONTIG(X);
+  CHECK_CUDA(nodes_explain);
+  CHECK_CONTIG(nodes_explain);
+  CHECK_CUDA(ncount);
+  CHECK_CONTIG(ncount);
+  check_x(X);
+  TORCH_CHECK(nodes_explain.dim() == 3 && nodes_explain.size(2) == 4 &&
+                  nodes_explain.scalar_type() == torch::kInt32,
+              "nodes must be explain records int32 [T, max_nodes, 4]");
+  int64_t N = X.size(0), d = X.size(1);
+  int64_t T = nodes_explain.size(0), max_nodes = nodes_explain.size(1);
+  TORCH_CHECK(ncount.scalar_type() == torch::kInt32 && ncount.dim() == 1 &&
+                  ncount.size(0) == T,
+              "ncount must be int32 [T]");
+  TORCH_CHECK(T >= 1, "explain needs at least one tree");
+  TORCH_CHECK(d >= 1 && d <= 4094,
+              "explain supports 1 <= d <= 4094 (12-bit feature field plus "
+              "the leaf sentinel column)");
+  TORCH_CHECK(max_nodes >= 1 && max_nodes <= 32767,
+              "explain records hold 15-bit node ids");
+  TORCH_CHECK(height_limit >= 1, "height_limit must be >= 1");
+  const auto out_opts = X.options().dtype(torch::kFloat32);
+  if (N == 0) return torch::empty({N, d}, out_opts);
+
+  const bool bf16 = is_bf16(X);
+  const size_t elem = bf16 ? 2 : 4;
+  const size_t budget = 150 * 1024;
+  // odd-WORD strides (all LDS banks hit) with room for column d: the key
+  // sentinel in the row tile, the self-loop sink in the accumulator tile
+  int64_t dpad = d + 1;
+  if (bf16) {
+    while (dpad % 4 != 2) ++dpad;
+  } else {
+    while (dpad % 2 != 1) ++dpad;
+  }
+  const int64_t astride = (d + 1) | 1;
+  const size_t tree_b = (size_t)max_nodes * 16;
+  const size_t rows_b = (size_t)256 * dpad * elem;
+  const size_t acc_b = (size_t)256 * astride * 4;
+  // deep forests overflow LDS node staging: records come from global/L2
+  const bool nodes_lds = tree_b <= 64 * 1024;
+  const size_t nb1 = nodes_lds ? tree_b : 0;
+  // accumulator routing: LDS tile, else the pre-zeroed out itself; rows
+  // that do not fit even alone are read from X
+  int mode = nb1 + rows_b + acc_b <= budget ? 0
+             : (nb1 + rows_b <= budget ? 1 : 2);
+  if (const char* e = getenv("IFA_EXPLAIN_FORCE_GLOBAL_ACC"))
+    if (atoi(e) && mode == 0) mode = 1;
+  // the LDS-tile flush writes every cell; the global routes add into out
+  auto out = mode == 0 ? torch::empty({N, d}, out_opts)
+                       : torch::zeros({N, d}, out_opts);
+  // (rpt, trees per barrier): most resident blocks first, then rows per
+  // thread (independent chains), then fewer barriers
+  const size_t row_unit = mode == 0 ? rows_b + acc_b : (mode == 1 ? rows_b : 0);
+  int rpt = 1, tps = 1;
+  size_t lds = nb1 + row_unit;
+  {
+    int best_blocks = 0, best_rpt = 0, best_tps = 0;
+    for (int r = (mode == 0 ? 2 : 1); r >= 1; --r) {
+      for (int s = 4; s >= 1; s >>= 1) {
+        if (!nodes_lds && s != 1) continue;
+        size_t l = (size_t)s * nb1 + (size_t)r * row_unit;
+        if (l > budget) continue;
+        int blocks_cu =
+            (int)std::min<size_t>(kMaxLds / std::max(l, (size_t)1), 4);
+        if (blocks_cu > best_blocks ||
+            (blocks_cu == best_blocks &&
+             (r > best_rpt || (r == best_rpt && s > best_tps)))) {
+          best_blocks = blocks_cu;
+          best_rpt = r;
+          best_tps = s;
+          rpt = r;
+          tps = s;
+          lds = l;
+        }
+      }
+    }
+  }
+  if (!nodes_lds) tps = (int)std::min<int64_t>(T, 1 << 30);  // one barrier
+  int64_t max_blocks = 8192;
+  if (const char* e = getenv("IFA_EXPLAIN_MAX_BLOCKS")) {
+    const int64_t v = atoll(e);
+    if (v >= 1) max_blocks = std::min<int64_t>(v, 8192);
+  }
+  const int64_t rows_per_block = (int64_t)rpt * 256;
+  int blocks = (int)std::min<int64_t>(
+      (N + rows_per_block - 1) / rows_per_block, max_blocks);
+  ifa::launch_explain_forest(
+      bf16, mode, rpt, nodes_lds, X.data_ptr(),
+      nodes_explain.data_ptr<int32_t>(), ncount.data_ptr<int32_t>(),
+      out.data_ptr<float>(), N, (int32_t)d, (int32_t)dpad, (int32_t)astride,
+      (int32_t)T, (int32_t)max_nodes, (int32_t)tps, (int32_t)height_limit,
+      (float)T, finalize ? 1 : 0, lds, blocks, current_stream());
+  return out;
+}
+
+// Per-feature attribution, extended forests (explain_extended_kernel).
+torch::Tensor explain_extended_forest(torch::Tensor X,
+                                      torch::Tensor nodes_packed,
+                                      torch::Tensor hidx, torch::Tensor hw,
+                                      torch::Tensor dl, torch::Tensor dr,
+                                      bool finalize) {
+  CHECK_CUDA(X);
+  CHECK_CONTIG(X);
+  CHECK_CUDA(nodes_packed);
+  CHECK_CONTIG(nodes_packed);
+  CHECK_CUDA(hidx);
+  CHECK_CONTIG(hidx);
+  CHECK_CUDA(hw);
+  CHECK_CONTIG(hw);
+  CHECK_CUDA(dl);
+  CHECK_CONTIG(dl);
+  CHECK_CUDA(dr);
+  CHECK_CONTIG(dr);
+  check_x(X);
+  TORCH_CHECK(nodes_packed.dim() == 3 && nodes_packed.size(2) == 2 &&
+                  nodes_packed.scalar_type() == torch::kInt32,
+              "nodes must be packed int32 [T, max_nodes, 2]");
+  int64_t N = X.size(0), d = X.size(1);
+  int64_t T = nodes_packed.size(0), max_nodes = nodes_packed.size(1);
+  TORCH_CHECK(hidx.dim() == 3 && hidx.scalar_type() == torch::kInt32 &&
+                  hidx.size(0) == T && hidx.size(1) == max_nodes,
+              "hidx must be int32 [T, max_nodes, nnz]");
+  int64_t nnz = hidx.size(2);
+  TORCH_CHECK(hw.scalar_type() == torch::kFloat32 &&
+                  hw.sizes() == hidx.sizes(),
+              "hw must be float32 [T, max_nodes, nnz]");
+  TORCH_CHECK(dl.scalar_type() == torch::kFloat32 &&
+                  dl.sizes() == hidx.sizes() &&
+                  dr.scalar_type() == torch::kFloat32 &&
+                  dr.sizes() == hidx.sizes(),
+              "edge deltas must be float32 [T, max_nodes, nnz]");
+  TORCH_CHECK(T >= 1, "explain needs at least one tree");
+  TORCH_CHECK(d >= 1 && d <= 4095, "explain supports 1 <= d <= 4095");
+  TORCH_CHECK(max_nodes <= 32767, "packed records hold 15-bit node ids");
+  auto out = torch::zeros({N, d}, X.options().dtype(torch::kFloat32));
+  if (N == 0) return out;
+  int64_t max_blocks = 8192;
+  if (const char* e = getenv("IFA_EXPLAIN_MAX_BLOCKS")) {
+    const int64_t v = atoll(e);
+    if (v >= 1) max_blocks = std::min<int64_t>(v, 8192);
+  }
+  int blocks = (int)std::min<int64_t>((N + 255) / 256, max_blocks);
+  ifa::launch_explain_extended(
+      is_bf16(X), X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
+      hidx.data_ptr<int32_t>(), hw.data_ptr<float>(), dl.data_ptr<float>(),
+      dr.data_ptr<float>(), out.data_ptr<float>(), N, (int32_t)d, (int32_t)T,
+      (int32_t)max_nodes, (int32_t)nnz, (float)T, finalize ? 1 : 0, blocks,
+      current_stream());
+  return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bag_gather", &bag_gather, "gather per-tree bags (K9/K10)");
   m.def("build_forest", &build_forest, "build standard iTrees (K1/K2/K11)");
@@ -620,5 +793,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "wide-format standard scoring (no packed-field limits)");
   m.def("score_extended_wide", &score_extended_wide,
         "wide-format EIF scoring (no packed-field limits)");
+  m.def("explain_forest", &explain_forest,
+        "per-feature path-length attribution, standard forests");
+  m.def("explain_extended_forest", &explain_extended_forest,
+        "per-feature path-length attribution, extended forests");
   m.attr("WAVE") = 64;
 }

@@ -1501,6 +1501,206 @@ __global__ void __launch_bounds__(256) score_extended_wide(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Per-feature attribution (docs/DESIGN.md §8): the v4 fixed-trip walk over
+// integer keys with one more thing carried along. Node records are 16 B
+// {feat | right<<12, key threshold, delta_left bits, delta_right bits};
+// leaves and pads self-loop with feat = d (the sentinel column) and both
+// deltas +0.0, so the walk needs no leaf test. A row visiting internal node
+// v adds the taken edge's f32 delta to acc[row][feat(v)].
+//
+// The contract is BITWISE vs cpu_engine.feature_contributions, so a row's
+// adds happen in one fixed order: trees 0..T-1, root to leaf. A row's trees
+// are therefore walked one after another; the independent chains that hide
+// LDS latency are the RPT rows a thread owns (plus the other resident
+// waves), never several trees of one row. Each thread owns its rows
+// outright: no atomics anywhere.
+//
+// ACC_LDS: accumulators live in an LDS tile [rows][astride] (odd word
+// stride; column d absorbs the self-loop +0.0 adds), zeroed per row tile and
+// flushed coalesced. Otherwise they are the pre-zeroed out[N][d] itself
+// (thread-owned, L2-resident), with the add predicated on f < d.
+// ROWS_LDS: keys staged in LDS with the sentinel column, as in v4; else
+// read from X and keyed per visit. NODES_LDS: `tps` trees staged per
+// barrier; else node records come from global/L2 (deep forests).
+// ---------------------------------------------------------------------------
+
+// f32 quotient that is correctly rounded by construction: f64 divide, then
+// one rounding (53 >= 2*24+2), so it equals numpy's f32 divide bit for bit.
+// Same detour as the hyperplane normalisation in
+// build_extended_forest_kernel (whose note records a 1-ulp miss of
+// __fdiv_rn) and the mean in score_forest_v4; whether the plain f32 divide
+// would also do here has not been measured.
+__device__ __forceinline__ float div32_exact(float a, float b) {
+  return (float)((double)a / (double)b);
+}
+
+template <typename KT, int RPT, bool ACC_LDS, bool ROWS_LDS, bool NODES_LDS>
+__global__ void __launch_bounds__(256) explain_forest_kernel(
+    const KT* __restrict__ X,          // raw bf16/f32 bits [N][d]
+    const int4* __restrict__ nodes,    // [T][max_nodes] explain records
+    const int32_t* __restrict__ ncnt,  // [T]
+    float* __restrict__ out,           // [N][d] (pre-zeroed when !ACC_LDS)
+    int64_t N, int32_t d, int32_t dpad, int32_t astride, int32_t T,
+    int32_t max_nodes, int32_t tps, int32_t height_limit, float fT,
+    int32_t finalize) {
+  const int tid = threadIdx.x;
+  const int rows_per_iter = RPT * 256;
+
+  int4* tlds = (int4*)smem;  // [tps * max_nodes] when NODES_LDS
+  float* acc = (float*)(tlds + (NODES_LDS ? tps * max_nodes : 0));
+  KT* rows = (KT*)(acc + (ACC_LDS ? rows_per_iter * astride : 0));
+
+  for (int64_t block_row0 = (int64_t)blockIdx.x * rows_per_iter; block_row0 < N;
+       block_row0 += (int64_t)gridDim.x * rows_per_iter) {
+    const int rows_here = (int)min((int64_t)rows_per_iter, N - block_row0);
+
+    __syncthreads();  // previous tile's flush / readers done
+    if (ROWS_LDS) {
+      const int64_t total = (int64_t)rows_here * d;
+      for (int64_t g = tid; g < total; g += 256) {
+        const int r = (int)(g / (uint32_t)d), c = (int)(g % (uint32_t)d);
+        rows[r * dpad + c] = key_of_bits<KT>(X[(block_row0 + r) * d + c]);
+      }
+      for (int r = tid; r < rows_per_iter; r += 256)
+        rows[r * dpad + d] = (KT)~(KT)0;  // leaf sentinel column
+    }
+    if (ACC_LDS)
+      for (int i = tid; i < rows_per_iter * astride; i += 256) acc[i] = 0.f;
+    // (the staging barrier below orders these writes before the walk)
+
+    const KT* rb[RPT];
+    float* ab[RPT];
+    int64_t my_row[RPT];
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+      rb[r] = rows + (tid + r * 256) * dpad;
+      ab[r] = acc + (tid + r * 256) * astride;
+      my_row[r] = block_row0 + tid + r * 256;
+    }
+
+    for (int t0 = 0; t0 < T; t0 += tps) {
+      const int nst = min(tps, T - t0);
+      __syncthreads();
+      if (NODES_LDS) {
+        for (int s = 0; s < nst; ++s) {
+          const int ncs = ncnt[t0 + s];
+          const int4* ss = nodes + (int64_t)(t0 + s) * max_nodes;
+          for (int i = tid; i < ncs; i += 256) tlds[s * max_nodes + i] = ss[i];
+        }
+        __syncthreads();
+      }
+      for (int s = 0; s < nst; ++s) {  // a row's trees: strictly in order
+        const int4* nb = NODES_LDS ? tlds + s * max_nodes
+                                   : nodes + (int64_t)(t0 + s) * max_nodes;
+        int cur[RPT];
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) cur[r] = 0;
+
+#pragma unroll 2
+        for (int it = 0; it < height_limit; ++it) {
+          int4 nd[RPT];
+#pragma unroll
+          for (int r = 0; r < RPT; ++r) nd[r] = nb[cur[r]];
+          uint32_t x[RPT];
+#pragma unroll
+          for (int r = 0; r < RPT; ++r) {
+            const int f = pn_feat(nd[r].x);
+            if (ROWS_LDS) {
+              x[r] = widen_key(rb[r][f]);
+            } else {
+              // the sentinel column does not exist in X: guard it
+              x[r] = (f < d && my_row[r] < N)
+                         ? widen_key(key_of_bits<KT>(X[my_row[r] * d + f]))
+                         : 0xFFFFFFFFu;
+            }
+          }
+#pragma unroll
+          for (int r = 0; r < RPT; ++r) {
+            const int f = pn_feat(nd[r].x);
+            const bool left = x[r] < (uint32_t)nd[r].y;
+            const float delta = __int_as_float(left ? nd[r].z : nd[r].w);
+            if (ACC_LDS) {
+              ab[r][f] = __fadd_rn(ab[r][f], delta);
+            } else if (f < d && my_row[r] < N) {
+              float* o = out + my_row[r] * d + f;
+              *o = __fadd_rn(*o, delta);
+            }
+            cur[r] = left ? cur[r] + 1 : pn_right(nd[r].x);
+          }
+        }
+      }
+    }
+
+    if (ACC_LDS) {
+      __syncthreads();  // every row's accumulators final
+      const int64_t total = (int64_t)rows_here * d;
+      for (int64_t g = tid; g < total; g += 256) {
+        const int r = (int)(g / (uint32_t)d), c = (int)(g % (uint32_t)d);
+        const float v = acc[r * astride + c];
+        out[(block_row0 + r) * d + c] = finalize ? div32_exact(v, fT) : v;
+      }
+    } else if (finalize) {
+#pragma unroll
+      for (int r = 0; r < RPT; ++r)
+        if (my_row[r] < N)
+          for (int c = 0; c < d; ++c) {
+            float* o = out + my_row[r] * d + c;
+            *o = div32_exact(*o, fT);
+          }
+    }
+  }
+}
+
+// EIF attribution: one thread per row, everything from global memory, the
+// strict j-order dot of score_extended_forest_kernel, walk until the leaf.
+// The taken edge's per-coordinate f32 shares (host-computed, [T][mn][nnz])
+// are added to the pre-zeroed out[row][hidx[j]] in ascending j over the
+// node's k = meta & 0xFFF coordinates. Bitwise vs
+// cpu_engine.feature_contributions_extended at every extension level.
+template <typename XT>
+__global__ void __launch_bounds__(256) explain_extended_kernel(
+    const XT* __restrict__ X, const int2* __restrict__ nodes,
+    const int32_t* __restrict__ hidx_g,  // [T][max_nodes][nnz]
+    const float* __restrict__ hw_g,      // [T][max_nodes][nnz]
+    const float* __restrict__ dl_g,      // [T][max_nodes][nnz]
+    const float* __restrict__ dr_g,      // [T][max_nodes][nnz]
+    float* __restrict__ out,             // [N][d] pre-zeroed
+    int64_t N, int32_t d, int32_t T, int32_t max_nodes, int32_t nnz,
+    float fT, int32_t finalize) {
+  for (int64_t my_row = (int64_t)blockIdx.x * 256 + threadIdx.x; my_row < N;
+       my_row += (int64_t)gridDim.x * 256) {
+    float* orow = out + my_row * d;
+    for (int t = 0; t < T; ++t) {
+      const int2* base = nodes + (int64_t)t * max_nodes;
+      const int64_t hbase = (int64_t)t * max_nodes * nnz;
+      int cur = 0;
+      while (true) {
+        const int2 nd = base[cur];
+        if (nd.x < 0) break;
+        const int64_t hoff = hbase + (int64_t)cur * nnz;
+        const int32_t* ci = hidx_g + hoff;
+        const float* cw = hw_g + hoff;
+        float dot = 0.f;
+        for (int j = 0; j < nnz; ++j) {
+          const float xv = load_feat<XT>(X, my_row * d + ci[j]);
+          dot = __fadd_rn(dot, __fmul_rn(cw[j], xv));
+        }
+        const bool left = dot < __int_as_float(nd.y);
+        const float* dj = (left ? dl_g : dr_g) + hoff;
+        const int k = min(pn_feat(nd.x), nnz);
+        for (int j = 0; j < k; ++j) {
+          float* o = orow + ci[j];
+          *o = __fadd_rn(*o, dj[j]);
+        }
+        cur = left ? cur + 1 : pn_right(nd.x);
+      }
+    }
+    if (finalize)
+      for (int c = 0; c < d; ++c) orow[c] = div32_exact(orow[c], fT);
+  }
+}
+
 }  // namespace ifa
 
 // ---------------------------------------------------------------------------
@@ -1815,6 +2015,57 @@ void launch_score_extended_forest(bool bf16, bool rows_lds, bool hyper_lds,
     else LSE(float, false, false);
   }
 #undef LSE
+}
+
+// mode: 0 = accumulators + rows in LDS (rpt 1 or 2), 1 = global
+// accumulators with rows in LDS, 2 = global accumulators and global rows
+void launch_explain_forest(bool bf16, int mode, int rpt, bool nodes_lds,
+                           const void* X, const void* nodes,
+                           const int32_t* ncount, float* out, int64_t N,
+                           int32_t d, int32_t dpad, int32_t astride,
+                           int32_t T, int32_t max_nodes, int32_t tps,
+                           int32_t height_limit, float fT, int finalize,
+                           size_t lds, int blocks, hipStream_t stream) {
+#define LX(KT, RPT, AL, RL, NL)                                               \
+  do {                                                                        \
+    raise_lds((const void*)explain_forest_kernel<KT, RPT, AL, RL, NL>, lds);  \
+    hipLaunchKernelGGL((explain_forest_kernel<KT, RPT, AL, RL, NL>),          \
+                       dim3(blocks), dim3(256), lds, stream, (const KT*)X,    \
+                       (const int4*)nodes, ncount, out, N, d, dpad, astride,  \
+                       T, max_nodes, tps, height_limit, fT, finalize);        \
+  } while (0)
+#define LX_MODE(KT, NL)                                                       \
+  do {                                                                        \
+    if (mode == 0 && rpt == 2) LX(KT, 2, true, true, NL);                     \
+    else if (mode == 0) LX(KT, 1, true, true, NL);                            \
+    else if (mode == 1) LX(KT, 1, false, true, NL);                           \
+    else LX(KT, 1, false, false, NL);                                         \
+  } while (0)
+  if (bf16) {
+    if (nodes_lds) LX_MODE(uint16_t, true); else LX_MODE(uint16_t, false);
+  } else {
+    if (nodes_lds) LX_MODE(uint32_t, true); else LX_MODE(uint32_t, false);
+  }
+#undef LX_MODE
+#undef LX
+}
+
+void launch_explain_extended(bool bf16, const void* X, const void* nodes,
+                             const int32_t* hidx, const float* hw,
+                             const float* dl, const float* dr, float* out,
+                             int64_t N, int32_t d, int32_t T,
+                             int32_t max_nodes, int32_t nnz, float fT,
+                             int finalize, int blocks, hipStream_t stream) {
+  if (bf16)
+    hipLaunchKernelGGL((explain_extended_kernel<uint16_t>), dim3(blocks),
+                       dim3(256), 0, stream, (const uint16_t*)X,
+                       (const int2*)nodes, hidx, hw, dl, dr, out, N, d, T,
+                       max_nodes, nnz, fT, finalize);
+  else
+    hipLaunchKernelGGL((explain_extended_kernel<float>), dim3(blocks),
+                       dim3(256), 0, stream, (const float*)X,
+                       (const int2*)nodes, hidx, hw, dl, dr, out, N, d, T,
+                       max_nodes, nnz, fT, finalize);
 }
 
 }  // namespace ifa

@@ -35,6 +35,14 @@ class ScoreResponse(BaseModel):
     labels: Optional[List[int]] = None  # only when a threshold is set
 
 
+class ExplainResponse(BaseModel):
+    # contributions[i][f] < 0: feature f made row i MORE anomalous;
+    # expectedPathLength + sum(contributions[i]) = row i's mean path length
+    contributions: List[List[float]]
+    expectedPathLength: float
+    scores: List[float]
+
+
 def create_app(model_path: str, device: str = None) -> FastAPI:
     if device is None:
         device = "cuda:0" if torch.cuda.is_available() else "cpu"
@@ -66,10 +74,7 @@ def create_app(model_path: str, device: str = None) -> FastAPI:
             "device": str(dev),
         }
 
-    @app.post("/v1/score", response_model=ScoreResponse)
-    def score(req: ScoreRequest):
-        if not req.instances:
-            return ScoreResponse(scores=[])
+    def parse_instances(req: ScoreRequest) -> np.ndarray:
         try:
             X = np.asarray(req.instances, dtype=np.float32)
         except ValueError:
@@ -81,6 +86,13 @@ def create_app(model_path: str, device: str = None) -> FastAPI:
                 status_code=400,
                 detail=f"each instance must have {d} features, "
                        f"got shape {list(X.shape)}")
+        return X
+
+    @app.post("/v1/score", response_model=ScoreResponse)
+    def score(req: ScoreRequest):
+        if not req.instances:
+            return ScoreResponse(scores=[])
+        X = parse_instances(req)
         try:
             with torch.no_grad():
                 scores = model.score(torch.from_numpy(X).to(dev))
@@ -95,5 +107,27 @@ def create_app(model_path: str, device: str = None) -> FastAPI:
         if threshold >= 0:
             labels = (scores_np >= threshold).astype(int).tolist()
         return ScoreResponse(scores=scores_np.tolist(), labels=labels)
+
+    @app.post("/v1/explain", response_model=ExplainResponse)
+    def explain(req: ScoreRequest):
+        """Per-feature contributions next to the scores (same request shape
+        and validation as /v1/score)."""
+        if not req.instances:
+            return ExplainResponse(
+                contributions=[], scores=[],
+                expectedPathLength=model.expected_path_length)
+        X = parse_instances(req)
+        try:
+            with torch.no_grad():
+                Xt = torch.from_numpy(X).to(dev)
+                contrib = model.feature_contributions(Xt)
+                scores = model.score(Xt)
+        except (IndexError, RuntimeError, ValueError) as e:
+            raise HTTPException(status_code=400,
+                                detail=f"explain failed: {e}")
+        return ExplainResponse(
+            contributions=contrib.float().cpu().numpy().tolist(),
+            expectedPathLength=model.expected_path_length,
+            scores=scores.float().cpu().numpy().tolist())
 
     return app

@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""Attribution microbench: time feature_contributions() and score() on the
+same resident matrix in one process.
+
+Usage: python tools/explain_bench.py [--rows 5000000] [--features 32]
+       [--trees 1000] [--dtype bf16] [--reps 5] [--warmup 2] [--extended]
+
+Both calls are warmed up, every repetition is bracketed by device
+synchronises, the two calls alternate (same process, same matrix, same
+model) and the MEDIAN repetition is reported. Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def timed(fn, X):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn(X)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=5_000_000)
+    ap.add_argument("--features", type=int, default=32)
+    ap.add_argument("--trees", type=int, default=1000)
+    ap.add_argument("--max-samples", type=int, default=256)
+    ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--extended", action="store_true")
+    ap.add_argument("--extension-level", type=int, default=None)
+    args = ap.parse_args()
+
+    from isolation_forest_amd import ExtendedIsolationForest, IsolationForest
+    from isolation_forest_amd.ops import load_extension
+
+    load_extension()
+    if not torch.cuda.is_available():
+        raise SystemExit("explain_bench needs a GPU; it has no CPU fallback")
+    dev = "cuda:0"
+    g = torch.Generator(device=dev)
+    g.manual_seed(7)
+    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+    X = torch.randn((args.rows, args.features), device=dev,
+                    generator=g).to(dtype)
+
+    cls = ExtendedIsolationForest if args.extended else IsolationForest
+    kw = {}
+    if args.extended and args.extension_level is not None:
+        kw["extensionLevel"] = args.extension_level
+    model = cls(numEstimators=args.trees, maxSamples=float(args.max_samples),
+                randomSeed=3, **kw).fit(X)
+
+    for _ in range(args.warmup):
+        model.feature_contributions(X)
+        model.score(X)
+    t_explain, t_score = [], []
+    for _ in range(args.reps):
+        dt, contrib = timed(model.feature_contributions, X)
+        t_explain.append(dt)
+        dt, scores = timed(model.score, X)
+        t_score.append(dt)
+    te = statistics.median(t_explain)
+    ts = statistics.median(t_score)
+    print(json.dumps({
+        "kernel": "explain_extended" if args.extended else "explain",
+        "ext_level": args.extension_level if args.extended else None,
+        "rows": args.rows, "features": args.features, "trees": args.trees,
+        "max_samples": args.max_samples, "dtype": args.dtype,
+        "reps": args.reps, "warmup": args.warmup,
+        "explain_ms_median": round(te * 1e3, 3),
+        "explain_ms_all": [round(t * 1e3, 3) for t in t_explain],
+        "explain_rows_per_s": round(args.rows / te),
+        "score_ms_median": round(ts * 1e3, 3),
+        "score_ms_all": [round(t * 1e3, 3) for t in t_score],
+        "score_rows_per_s": round(args.rows / ts),
+        "explain_over_score_time": round(te / ts, 3),
+        "expected_path_length": model.expected_path_length,
+        "sample_contributions": [
+            round(float(v), 6) for v in contrib[0, :4].float().cpu()],
+        "sample_scores": [round(float(v), 6) for v in scores[:4].float().cpu()],
+    }))
+
+
+if __name__ == "__main__":
+    main()
