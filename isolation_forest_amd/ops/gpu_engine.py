@@ -18,8 +18,8 @@ width and dtype (score_extended_forest):
   fall through to the strict kernels),
 * nnz <= 5 uniform -> sparse v2 (bitwise strict j-order),
 * densifiable (nnz == d or nnz >= 6): bf16 rows -> dense v3 (packed
-  bf16 weights, d <= 128), f32 rows -> dense v2 (d <= 64) — tolerance
-  contracts per PARITY.md; a batch with a non-finite cell and nnz < d
+  bf16 weights, d <= 128), f32 and fp16 rows -> dense v2 (d <= 64; fp16
+  rows widen exactly to f32 at load) — tolerance contracts per PARITY.md; a batch with a non-finite cell and nnz < d
   skips the densified route (0 * inf = NaN) for the general kernel,
 * otherwise (wide d, ragged widths, LDS overflow) -> the general
   strict-order kernel; forests past the packed 15-bit-node/12-bit-
@@ -156,7 +156,36 @@ def build_extended_forest(X: torch.Tensor, bag_idx: np.ndarray,
 # ---------------------------------------------------------------------------
 
 
+# Row dtype kinds. The packing routines and cache keys below take a `kind`:
+# "f32", "bf16" or "f16". The bool spelling (False = f32, True = bf16)
+# predates fp16 rows and is still accepted everywhere.
+_ROW_KINDS = {
+    torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16",
+    False: "f32", True: "bf16", "f32": "f32", "bf16": "bf16", "f16": "f16",
+}
+
+
+def _row_kind(x) -> str:
+    """Normalise a torch dtype / bool / kind string to the kind string."""
+    try:
+        return _ROW_KINDS[x]
+    except (KeyError, TypeError):
+        raise ValueError(f"unsupported row dtype {x!r}: GPU rows are float32, "
+                         "bfloat16 or float16") from None
+
+
+def _threshold_keys(split_vals: np.ndarray, kind) -> np.ndarray:
+    """Integer key thresholds (u32) of f32 split values for a row kind."""
+    kind = _row_kind(kind)
+    if kind == "bf16":
+        return _bf16_threshold_keys(split_vals)
+    if kind == "f16":
+        return _f16_threshold_keys(split_vals)
+    return _key32(split_vals)
+
+
 _BF16_KEY_TABLES = None
+_F16_KEY_TABLES = None
 
 
 def _bf16_key_tables():
@@ -177,6 +206,53 @@ def _bf16_key_tables():
         ok[0x7FFF] = False  # -0's raw key: never staged
         _BF16_KEY_TABLES = (vals[ok].copy(), keys[ok].astype(np.uint32))
     return _BF16_KEY_TABLES
+
+
+def _key16_f16(bits: np.ndarray) -> np.ndarray:
+    """Order-preserving u16 key of fp16 BIT patterns (device key16_f16()):
+    the bf16 sign-magnitude fold, with NaN at m > 0x7C00."""
+    b = np.asarray(bits).astype(np.uint32)
+    m = b & np.uint32(0x7FFF)
+    k = np.where(b & np.uint32(0x8000),
+                 np.uint32(0x7FFF) - m,
+                 np.uint32(0x8000) + m).astype(np.uint32)
+    k[m == 0] = np.uint32(0x8000)
+    k[m > np.uint32(0x7C00)] = np.uint32(0xFFFF)
+    return k
+
+
+def _f16_key_tables():
+    """(values, keys) of every producible fp16 KEY, value-ascending: the
+    63,489 keys of finite and +-inf fp16 values, without 0x7FFF (-0 maps to
+    +0's key). Values are the exact f32 widenings."""
+    global _F16_KEY_TABLES
+    if _F16_KEY_TABLES is None:
+        keys = np.arange(65536, dtype=np.uint32)
+        pos = keys >= 0x8000
+        bits = np.where(pos, keys - 0x8000,
+                        0x8000 + (0x7FFF - keys)).astype(np.uint16)
+        vals = bits.view(np.float16).astype(np.float32)
+        ok = ~np.isnan(vals)
+        ok[0x7FFF] = False  # -0's raw key: never staged
+        _F16_KEY_TABLES = (vals[ok].copy(), keys[ok].astype(np.uint32))
+    return _F16_KEY_TABLES
+
+
+def _f16_threshold_keys(split_vals: np.ndarray) -> np.ndarray:
+    """Smallest producible fp16 key whose value is >= the f32 split value,
+    shifted into the high 16 bits (kernel compares widened keys), so that
+    widen(key(x)) < threshold  <=>  f32(x) < s  for every fp16 x.
+
+    Table + searchsorted(side="left"). Splits outside fp16's range (foreign
+    models) land where they must: s > 65504 -> the +inf key, s < -65504 ->
+    the key of -65504, 0 < s < 2^-24 -> the smallest subnormal's key. A NaN
+    split sorts past the table and gets key 0: nothing compares below it,
+    as `x < NaN` is false in the oracle."""
+    vals, keys = _f16_key_tables()
+    s = np.ascontiguousarray(split_vals, dtype=np.float32)
+    idx = np.searchsorted(vals, s, side="left")
+    keys_ext = np.append(keys, np.uint32(0))
+    return keys_ext[idx].astype(np.uint32) << np.uint32(16)
 
 
 def _key32(vals: np.ndarray) -> np.ndarray:
@@ -259,8 +335,9 @@ def _split_thresholds32(forest) -> np.ndarray:
                     v32).astype(np.float32)
 
 
-def _nodes_packed_v4(forest, d_sentinel: int, bf16: bool):
-    """v4 packed nodes for score_forest_v4 (see forest_kernels.hip):
+def _nodes_packed_v4(forest, d_sentinel: int, bf16):
+    """v4 packed nodes for score_forest_v4 (see forest_kernels.hip);
+    `bf16` is the row kind (_row_kind: False/"f32", True/"bf16", "f16"):
     w0 = feat | right<<12; internal w1 = integer key threshold; leaf:
     feat = d_sentinel, right = own id (self-loop), w1 = f32(depth + c(m)).
     Trees are padded to a multiple of 8 with single-leaf value-0 dummies
@@ -286,7 +363,7 @@ def _nodes_packed_v4(forest, d_sentinel: int, bf16: bool):
     w1 = np.zeros((T, mn), dtype=np.uint32)
     if internal.any():
         s = _split_thresholds32(forest)[internal]
-        w1[internal] = _bf16_threshold_keys(s) if bf16 else _key32(s)
+        w1[internal] = _threshold_keys(s, bf16)
     leafval = (depth.astype(np.float32) + val.astype(np.float32))
     w1[leaf] = leafval[leaf].astype(np.float32).view(np.uint32)
     pad = (-T) % 8
@@ -306,9 +383,10 @@ def _nodes_packed_v4(forest, d_sentinel: int, bf16: bool):
     return packed, ncount, max(max_depth, 1)
 
 
-def _nodes_packed_wide(forest, bf16: bool):
+def _nodes_packed_wide(forest, bf16):
     """Wide int4 node records {feat, right, key_or_value, 0} for
-    score_forest_wide — no 12-bit feature / 15-bit node-id limits
+    score_forest_wide (`bf16` is the row kind, as in _nodes_packed_v4) —
+    no 12-bit feature / 15-bit node-id limits
     (the reference has no such size caps,
     IsolationTree.scala). Same key/leaf-value math as _nodes_packed_v4,
     so the walk stays bitwise vs cpu_engine.path_lengths. Leaves and pad
@@ -326,7 +404,7 @@ def _nodes_packed_wide(forest, bf16: bool):
     w2 = np.zeros((T, mn), dtype=np.uint32)
     if internal.any():
         s = _split_thresholds32(forest)[internal]
-        keys = _bf16_threshold_keys(s) if bf16 else _key32(s)
+        keys = _threshold_keys(s, bf16)
         w2[internal] = keys.astype(np.uint32)
     leafval = depth.astype(np.float32) + val.astype(np.float32)
     w2[leaf] = leafval[leaf].astype(np.float32).view(np.uint32)
@@ -339,8 +417,9 @@ def _nodes_packed_wide(forest, bf16: bool):
     return packed, max(max_depth, 1)
 
 
-def _nodes_packed_explain(forest, d_sentinel: int, bf16: bool):
-    """16-byte node records for explain_forest_kernel:
+def _nodes_packed_explain(forest, d_sentinel: int, bf16):
+    """16-byte node records for explain_forest_kernel (`bf16` is the row
+    kind, as in _nodes_packed_v4):
     {feat | right<<12, integer key threshold, delta_left bits,
     delta_right bits}. Threshold math is _nodes_packed_v4's; the f32 edge
     deltas are cpu_engine.explain_tables' (shared with the CPU oracle, so
@@ -368,7 +447,7 @@ def _nodes_packed_explain(forest, d_sentinel: int, bf16: bool):
     w1 = np.zeros((T, mn), dtype=np.uint32)
     if internal.any():
         s = _split_thresholds32(forest)[internal]
-        w1[internal] = _bf16_threshold_keys(s) if bf16 else _key32(s)
+        w1[internal] = _threshold_keys(s, bf16)
     packed = np.zeros((T, mn, 4), dtype=np.int32)
     packed[..., 0] = w0
     packed[..., 1] = w1.view(np.int32)
@@ -426,8 +505,10 @@ def _eif0_eligible(forest, d: int) -> bool:
     return flag
 
 
-def _eif0_packed_v4(forest, d_sentinel: int, bf16: bool):
-    """Pack an extensionLevel-0 EIF forest into STANDARD v4 node records,
+def _eif0_packed_v4(forest, d_sentinel: int, bf16):
+    """Pack an extensionLevel-0 EIF forest into STANDARD v4 node records
+    (`bf16` is the row kind, as in _nodes_packed_v4; 16-bit kinds search
+    their producible-key table, f32 the whole key range),
     so scoring reuses the unmodified fixed-trip walk (score_forest_v4)
     with NO per-visit multiply and NO extra compare.
 
@@ -469,8 +550,11 @@ def _eif0_packed_v4(forest, d_sentinel: int, bf16: bool):
     io = o[internal]
     iflip = flip[internal]
 
-    if bf16:
-        vals, keys = _bf16_key_tables()
+    kind = _row_kind(bf16)
+    if kind != "f32":
+        # 18 halvings cover both tables (bf16 65,279 keys, fp16 63,489)
+        vals, keys = (_bf16_key_tables() if kind == "bf16"
+                      else _f16_key_tables())
         lo = np.zeros(iw.shape, dtype=np.int64)
         hi = np.full(iw.shape, len(vals), dtype=np.int64)
         for _ in range(18):
@@ -657,6 +741,25 @@ def _bf16_threshold_keys_dev(vals_f32: torch.Tensor) -> torch.Tensor:
     return k << 16
 
 
+_F16_KEY_TABLES_DEV = {}
+
+
+def _f16_threshold_keys_dev(vals_f32: torch.Tensor) -> torch.Tensor:
+    """Device mirror of _f16_threshold_keys: int64 holding (t16 << 16).
+    The same table, uploaded once per device, and torch.searchsorted
+    (right=False is numpy's side="left")."""
+    dev = vals_f32.device
+    tabs = _F16_KEY_TABLES_DEV.get(str(dev))
+    if tabs is None:
+        vals, keys = _f16_key_tables()
+        keys_ext = np.append(keys, np.uint32(0)).astype(np.int64)
+        tabs = (torch.from_numpy(vals).to(dev),
+                torch.from_numpy(keys_ext).to(dev))
+        _F16_KEY_TABLES_DEV[str(dev)] = tabs
+    idx = torch.searchsorted(tabs[0], vals_f32.contiguous(), right=False)
+    return tabs[1][idx] << 16
+
+
 def _key32_dev(vals_f32: torch.Tensor) -> torch.Tensor:
     """Device mirror of _key32: int64 holding u32 keys (inputs never NaN)."""
     b = vals_f32.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
@@ -665,9 +768,11 @@ def _key32_dev(vals_f32: torch.Tensor) -> torch.Tensor:
     return torch.where(m == 0, torch.full_like(k, 0x80000000), k)
 
 
-def _nodes_packed_v4_device(raw, num_trees: int, d_sentinel: int, bf16: bool):
+def _nodes_packed_v4_device(raw, num_trees: int, d_sentinel: int, bf16):
     """Torch-side v4 packing from the raw build outputs still on device —
-    identical bit layout to _nodes_packed_v4, no host round trip."""
+    identical bit layout to _nodes_packed_v4 (`bf16` is the row kind), no
+    host round trip."""
+    kind = _row_kind(bf16)
     feat, value = raw["feat"], raw["value"]
     right, ncount, depth = raw["right"], raw["ncount"], raw["depth"]
     T, mn = feat.shape
@@ -681,7 +786,9 @@ def _nodes_packed_v4_device(raw, num_trees: int, d_sentinel: int, bf16: bool):
         feat | (right << 12),
         torch.tensor(d_sentinel, dtype=torch.int32, device=dev) | (ids << 12),
     )
-    tkeys = (_bf16_threshold_keys_dev(value) if bf16 else _key32_dev(value))
+    tkeys = (_bf16_threshold_keys_dev(value) if kind == "bf16"
+             else _f16_threshold_keys_dev(value) if kind == "f16"
+             else _key32_dev(value))
     leafbits = (depth.to(torch.float32) + value).view(torch.int32)
     w1 = torch.where(internal, _to_i32(tkeys),
                      torch.where(leaf, leafbits,
@@ -739,8 +846,15 @@ def _eif_dense_packed_device(raw, D: int):
 
 
 def _device_forest(model, device, v4_key=None):
-    """Cached device copy of the packed forest. v4_key = (d, bf16) selects
-    the standard-scoring v4 packing; None = the EIF packing."""
+    """Cached device copy of the packed forest. v4_key = (d, kind) selects
+    the standard-scoring v4 packing; None = the EIF packing. Packs that
+    hold integer key thresholds — (d, kind), ("wide", kind),
+    ("eif0", d, kind), ("explain", d, kind) — are keyed on the row KIND, not
+    on "is it 16-bit": bf16 and fp16 keys differ, and u32 records under a
+    u16 kernel score silently wrong."""
+    if isinstance(v4_key, tuple) and v4_key[0] not in ("eif_dense",
+                                                       "eif_dense3"):
+        v4_key = v4_key[:-1] + (_row_kind(v4_key[-1]),)
     key = (str(device), id(model.forest), v4_key)
     cache = model._gpu_forest_cache
     if key not in cache:
@@ -865,12 +979,12 @@ def _device_forest(model, device, v4_key=None):
             extra["hw"] = torch.from_numpy(
                 np.ascontiguousarray(forest.hyper_w)).to(device)
         elif v4_key is not None:
-            d, bf16 = v4_key
+            d, kind = v4_key
             if raw is not None:
                 aos, ncount, max_depth = _nodes_packed_v4_device(
-                    raw, forest.num_trees, d, bf16)
+                    raw, forest.num_trees, d, kind)
             else:
-                packed, ncount_np, max_depth = _nodes_packed_v4(forest, d, bf16)
+                packed, ncount_np, max_depth = _nodes_packed_v4(forest, d, kind)
                 aos = torch.from_numpy(packed).to(device)
                 ncount = torch.from_numpy(ncount_np).to(device)
             extra["height"] = max_depth
@@ -886,8 +1000,9 @@ def _device_forest(model, device, v4_key=None):
                 extra["hw"] = torch.from_numpy(
                     np.ascontiguousarray(forest.hyper_w)
                 ).to(device)
-        # bounded FIFO (a few packings per model: e.g. alternating bf16/f32
-        # scoring of one model keeps both — VERDICT r01 weak #6)
+        # bounded FIFO (a few packings per model: e.g. alternating
+        # bf16/fp16/f32 scoring of one model keeps all three — VERDICT r01
+        # weak #6)
         while len(cache) >= 4:
             cache.pop(next(iter(cache)))
         cache[key] = (aos, ncount, extra)
@@ -907,17 +1022,17 @@ def score_forest(model, X: torch.Tensor, finalize: bool = True) -> torch.Tensor:
     ext = load_extension()
     forest = model.forest
     d = int(X.shape[1])
-    bf16 = X.dtype == torch.bfloat16
+    kind = _row_kind(X.dtype)
     c = float(avg_path_length(forest.num_samples))
     if not _packed_fits(forest, d):
         # loaded/CPU-built forests past the packed-format caps: wide int4
         # records, no field-width limits
         aos, ncount, extra = _device_forest(
-            model, X.device, v4_key=("wide", bf16))
+            model, X.device, v4_key=("wide", kind))
         return ext.score_forest_wide(
             X.contiguous(), aos, extra["height"], c, finalize,
         )
-    aos, ncount, extra = _device_forest(model, X.device, v4_key=(d, bf16))
+    aos, ncount, extra = _device_forest(model, X.device, v4_key=(d, kind))
     return ext.score_forest(
         X.contiguous(), aos, ncount, forest.num_trees, extra["height"], c,
         finalize,
@@ -966,13 +1081,13 @@ def score_extended_forest(model, X: torch.Tensor, finalize: bool = True) -> torc
         # strict-order route below, whose dot reproduces the oracle's
         # NaN-compares-false behaviour)
         aos, ncount, extra = _device_forest(
-            model, X.device, v4_key=("eif0", d, X.dtype == torch.bfloat16))
+            model, X.device, v4_key=("eif0", d, _row_kind(X.dtype)))
         return ext.score_forest(
             X.contiguous(), aos, ncount, forest.num_trees, extra["height"],
             c, finalize,
         )
     if nnz <= 5 and _eif_uniform_nnz(forest):
-        elem = 2 if X.dtype == torch.bfloat16 else 4
+        elem = 4 if X.dtype == torch.float32 else 2  # bf16 / fp16
         dpad = d
         if elem == 2:
             while dpad % 4 != 2:
@@ -1053,9 +1168,9 @@ def _explain_on_cpu(fn, forest, X: torch.Tensor, finalize: bool, why: str):
 
 
 def _check_explain_input(X: torch.Tensor):
-    if X.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError("feature_contributions expects float32 or bfloat16 "
-                         f"rows on the GPU, got {X.dtype}")
+    if X.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError("feature_contributions expects float32, bfloat16 "
+                         f"or float16 rows on the GPU, got {X.dtype}")
 
 
 def explain_forest(model, X: torch.Tensor, finalize: bool = True) -> torch.Tensor:
@@ -1076,9 +1191,8 @@ def explain_forest(model, X: torch.Tensor, finalize: bool = True) -> torch.Tenso
             "forest exceeds the packed node format (15-bit node ids, "
             "12-bit feature ids)")
     ext = load_extension()
-    bf16 = X.dtype == torch.bfloat16
     aos, ncount, extra = _device_forest(
-        model, X.device, v4_key=("explain", d, bf16))
+        model, X.device, v4_key=("explain", d, _row_kind(X.dtype)))
     return ext.explain_forest(X.contiguous(), aos, ncount, extra["height"],
                               finalize)
 

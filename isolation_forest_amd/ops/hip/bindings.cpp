@@ -8,9 +8,11 @@
 
 #include <vector>
 
+#include "row_dtype.h"
+
 namespace ifa {
 
-void launch_bag_gather(bool bf16, const void* X, const int64_t* bag_idx,
+void launch_bag_gather(RowDtype dt, const void* X, const int64_t* bag_idx,
                        float* bags, int64_t T, int64_t n, int64_t d,
                        hipStream_t stream);
 
@@ -33,7 +35,7 @@ void launch_build_extended_forest(const float* bags, const int32_t* feat_sub,
                                   int32_t max_nodes, int32_t height_limit,
                                   size_t lds, hipStream_t stream);
 
-void launch_score_forest(bool bf16, int rpt, bool rows_lds, bool nodes_lds,
+void launch_score_forest(RowDtype dt, int rpt, bool rows_lds, bool nodes_lds,
                          int ilp, const void* X, const void* nodes,
                          const int32_t* ncount, float* out, int64_t N,
                          int32_t d, int32_t dpad, int32_t Tpad,
@@ -41,7 +43,7 @@ void launch_score_forest(bool bf16, int rpt, bool rows_lds, bool nodes_lds,
                          float c_norm, int finalize, size_t lds, int blocks,
                          hipStream_t stream);
 
-void launch_score_extended_dense(bool bf16, bool rows_lds, bool wlds,
+void launch_score_extended_dense(RowDtype dt, bool rows_lds, bool wlds,
                                  const void* X, const void* nodes,
                                  const float* hw, const int32_t* ncount,
                                  float* out, int64_t N, int32_t d,
@@ -49,7 +51,7 @@ void launch_score_extended_dense(bool bf16, bool rows_lds, bool wlds,
                                  float fT, float c_norm, int finalize,
                                  size_t lds, int blocks, hipStream_t stream);
 
-void launch_score_extended_forest(bool bf16, bool rows_lds, bool hyper_lds,
+void launch_score_extended_forest(RowDtype dt, bool rows_lds, bool hyper_lds,
                                   bool nodes_lds, const void* X,
                                   const void* nodes, const int32_t* hidx,
                                   const float* hw, const int32_t* ncount,
@@ -58,7 +60,7 @@ void launch_score_extended_forest(bool bf16, bool rows_lds, bool hyper_lds,
                                   float c_norm, int finalize, size_t lds,
                                   int blocks, hipStream_t stream);
 
-void launch_score_extended_sparse_v2(bool bf16, int nnz, const void* X,
+void launch_score_extended_sparse_v2(RowDtype dt, int nnz, const void* X,
                                      const void* nodes, const float* values,
                                      const int32_t* hidx, const float* hw,
                                      const int32_t* ncount, float* out,
@@ -68,7 +70,7 @@ void launch_score_extended_sparse_v2(bool bf16, int nnz, const void* X,
                                      float c_norm, int finalize, size_t lds,
                                      int blocks, hipStream_t stream);
 
-void launch_score_extended_dense_v2(bool bf16, int D, const void* X,
+void launch_score_extended_dense_v2(RowDtype dt, int D, const void* X,
                                     const void* nodes, const float* values,
                                     const float* hw, const int32_t* ncount,
                                     float* out, int64_t N, int32_t d,
@@ -88,24 +90,24 @@ void launch_score_extended_dense_v3(int D, bool rpt2, const void* X,
                                     hipStream_t stream);
 
 void launch_score_extended_dense_nonfinite_rows(
-    bool bf16, bool packed_w, const void* X, const void* nodes,
+    RowDtype dt, bool packed_w, const void* X, const void* nodes,
     const float* values, const void* wts, float* out, int64_t N, int32_t d,
     int32_t D, int32_t T, int32_t max_nodes, int32_t height_limit, float fT,
     float c_norm, int finalize, int blocks, hipStream_t stream);
-void launch_score_forest_wide(bool bf16, const void* X, const void* nodes,
+void launch_score_forest_wide(RowDtype dt, const void* X, const void* nodes,
                               float* out, int64_t N, int32_t d, int32_t T,
                               int64_t max_nodes, int32_t height_limit,
                               float fT, float c_norm, int finalize,
                               int blocks, hipStream_t stream);
 
-void launch_score_extended_wide(bool bf16, const void* X, const void* nodes,
+void launch_score_extended_wide(RowDtype dt, const void* X, const void* nodes,
                                 const int32_t* hidx, const float* hw,
                                 float* out, int64_t N, int32_t d, int32_t T,
                                 int64_t max_nodes, int32_t nnz, float fT,
                                 float c_norm, int finalize, int blocks,
                                 hipStream_t stream);
 
-void launch_explain_forest(bool bf16, int mode, int rpt, bool nodes_lds,
+void launch_explain_forest(RowDtype dt, int mode, int rpt, bool nodes_lds,
                            const void* X, const void* nodes,
                            const int32_t* ncount, float* out, int64_t N,
                            int32_t d, int32_t dpad, int32_t astride,
@@ -113,7 +115,7 @@ void launch_explain_forest(bool bf16, int mode, int rpt, bool nodes_lds,
                            int32_t height_limit, float fT, int finalize,
                            size_t lds, int blocks, hipStream_t stream);
 
-void launch_explain_extended(bool bf16, const void* X, const void* nodes,
+void launch_explain_extended(RowDtype dt, const void* X, const void* nodes,
                              const int32_t* hidx, const float* hw,
                              const float* dl, const float* dr, float* out,
                              int64_t N, int32_t d, int32_t T,
@@ -139,11 +141,19 @@ bool is_bf16(const torch::Tensor& t) {
   return t.scalar_type() == torch::kBFloat16;
 }
 
+// row element type of a checked X (check_x admits exactly these three)
+ifa::RowDtype row_dtype(const torch::Tensor& t) {
+  if (t.scalar_type() == torch::kBFloat16) return ifa::ROW_BF16;
+  if (t.scalar_type() == torch::kHalf) return ifa::ROW_F16;
+  return ifa::ROW_F32;
+}
+
 void check_x(const torch::Tensor& X) {
   TORCH_CHECK(X.dim() == 2, "X must be [N, d]");
-  TORCH_CHECK(
-      X.scalar_type() == torch::kFloat32 || X.scalar_type() == torch::kBFloat16,
-      "X must be float32 or bfloat16");
+  TORCH_CHECK(X.scalar_type() == torch::kFloat32 ||
+                  X.scalar_type() == torch::kBFloat16 ||
+                  X.scalar_type() == torch::kHalf,
+              "X must be float32, bfloat16 or float16");
 }
 
 }  // namespace
@@ -158,7 +168,7 @@ torch::Tensor bag_gather(torch::Tensor X, torch::Tensor bag_idx) {
               "bag_idx must be int64 [T, n]");
   int64_t T = bag_idx.size(0), n = bag_idx.size(1), d = X.size(1);
   auto bags = torch::empty({T, n, d}, X.options().dtype(torch::kFloat32));
-  ifa::launch_bag_gather(is_bf16(X), X.data_ptr(),
+  ifa::launch_bag_gather(row_dtype(X), X.data_ptr(),
                          bag_idx.data_ptr<int64_t>(), bags.data_ptr<float>(),
                          T, n, d, current_stream());
   return bags;
@@ -272,12 +282,12 @@ torch::Tensor score_forest(torch::Tensor X, torch::Tensor nodes_packed,
   auto out = torch::empty({N}, X.options().dtype(torch::kFloat32));
   if (N == 0) return out;
 
-  const bool bf16 = is_bf16(X);
-  const size_t elem = bf16 ? 2 : 4;
+  const ifa::RowDtype dt = row_dtype(X);
+  const size_t elem = (size_t)ifa::row_elem_bytes(dt);
   // odd-WORD row stride (all 32 LDS banks hit) with room for the sentinel
   // column at index d
   int64_t dpad = d + 1;
-  if (bf16) {
+  if (elem == 2) {
     while (dpad % 4 != 2) ++dpad;  // dpad u16 elems -> dpad/2 words, odd
   } else {
     while (dpad % 2 != 1) ++dpad;  // odd word count
@@ -332,7 +342,7 @@ torch::Tensor score_forest(torch::Tensor X, torch::Tensor nodes_packed,
   int64_t rows_per_block = (int64_t)(rows_lds ? rpt : 1) * 256;
   int blocks = (int)std::min<int64_t>(
       (N + rows_per_block - 1) / rows_per_block, 8192);
-  ifa::launch_score_forest(bf16, rpt, rows_lds, nodes_lds, ilp, X.data_ptr(),
+  ifa::launch_score_forest(dt, rpt, rows_lds, nodes_lds, ilp, X.data_ptr(),
                            nodes_packed.data_ptr<int32_t>(),
                            ncount.data_ptr<int32_t>(), out.data_ptr<float>(),
                            N, (int32_t)d, (int32_t)dpad, (int32_t)Tpad,
@@ -367,8 +377,8 @@ torch::Tensor score_extended_forest(torch::Tensor X,
   auto out = torch::empty({N}, X.options().dtype(torch::kFloat32));
   if (N == 0) return out;
 
-  const bool bf16 = is_bf16(X);
-  const size_t elem = bf16 ? 2 : 4;
+  const ifa::RowDtype dt = row_dtype(X);
+  const size_t elem = (size_t)ifa::row_elem_bytes(dt);
   const size_t pad = 16 / elem;
   size_t row_bytes = (size_t)256 * (d + pad) * elem;
   size_t node_bytes = (size_t)max_nodes * 8;
@@ -386,7 +396,7 @@ torch::Tensor score_extended_forest(torch::Tensor X,
         node_bytes + (wlds ? w_bytes : 0) + drow_bytes <= 152 * 1024;
     size_t lds = node_bytes + (wlds ? w_bytes : 0) + (rows_lds ? drow_bytes : 0);
     ifa::launch_score_extended_dense(
-        bf16, rows_lds, wlds, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
+        dt, rows_lds, wlds, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
         hw.data_ptr<float>(), ncount.data_ptr<int32_t>(),
         out.data_ptr<float>(), N, (int32_t)d, (int32_t)dpad, (int32_t)T,
         (int32_t)max_nodes, (float)T, (float)c_norm, finalize ? 1 : 0, lds,
@@ -404,7 +414,7 @@ torch::Tensor score_extended_forest(torch::Tensor X,
   size_t lds =
       nb + (hyper_lds ? hyper_bytes : 0) + (rows_lds ? row_bytes : 0);
   ifa::launch_score_extended_forest(
-      bf16, rows_lds, hyper_lds, nodes_lds, X.data_ptr(),
+      dt, rows_lds, hyper_lds, nodes_lds, X.data_ptr(),
       nodes_packed.data_ptr<int32_t>(), hidx.data_ptr<int32_t>(),
       hw.data_ptr<float>(), ncount.data_ptr<int32_t>(), out.data_ptr<float>(),
       N, (int32_t)d, (int32_t)T, (int32_t)max_nodes, (int32_t)nnz, (float)T,
@@ -445,14 +455,14 @@ torch::Tensor score_extended_dense_v2(torch::Tensor X,
   TORCH_CHECK(lds <= kMaxLds, "tree too large for LDS staging");
   int blocks = (int)std::min<int64_t>((N + 511) / 512, 8192);
   ifa::launch_score_extended_dense_v2(
-      is_bf16(X), D, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
+      row_dtype(X), D, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
       values.data_ptr<float>(), hw.data_ptr<float>(),
       ncount.data_ptr<int32_t>(), out.data_ptr<float>(), N, (int32_t)d,
       (int32_t)T, (int32_t)max_nodes, (int32_t)height_limit, (float)T,
       (float)c_norm, finalize ? 1 : 0, lds, blocks, current_stream());
   // rows with an inf/NaN cell: strict-order rescoring (see the kernel)
   ifa::launch_score_extended_dense_nonfinite_rows(
-      is_bf16(X), false, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
+      row_dtype(X), false, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
       values.data_ptr<float>(), hw.data_ptr<float>(), out.data_ptr<float>(),
       N, (int32_t)d, (int32_t)D, (int32_t)T, (int32_t)max_nodes,
       (int32_t)height_limit, (float)T, (float)c_norm, finalize ? 1 : 0,
@@ -476,7 +486,8 @@ torch::Tensor score_extended_dense_v3(torch::Tensor X,
   CHECK_CONTIG(hwp);
   CHECK_CUDA(ncount);
   check_x(X);
-  TORCH_CHECK(is_bf16(X), "dense v3 requires bf16 rows (f32 rows route to v2)");
+  TORCH_CHECK(is_bf16(X),
+              "dense v3 requires bf16 rows (f32/fp16 rows route to v2)");
   TORCH_CHECK(nodes_packed.dim() == 3 && nodes_packed.size(2) == 2 &&
                   nodes_packed.scalar_type() == torch::kInt32,
               "nodes must be packed int32 [T, max_nodes, 2]");
@@ -507,7 +518,7 @@ torch::Tensor score_extended_dense_v3(torch::Tensor X,
       (float)c_norm, finalize ? 1 : 0, lds, blocks, current_stream());
   // rows with an inf/NaN cell: strict-order rescoring (see the kernel)
   ifa::launch_score_extended_dense_nonfinite_rows(
-      true, true, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
+      ifa::ROW_BF16, true, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
       values.data_ptr<float>(), hwp.data_ptr<int32_t>(),
       out.data_ptr<float>(), N, (int32_t)d, (int32_t)D, (int32_t)T,
       (int32_t)max_nodes, (int32_t)height_limit, (float)T, (float)c_norm,
@@ -542,10 +553,10 @@ torch::Tensor score_extended_sparse_v2(torch::Tensor X,
   auto out = torch::empty({N}, X.options().dtype(torch::kFloat32));
   if (N == 0) return out;
 
-  const bool bf16 = is_bf16(X);
-  const size_t elem = bf16 ? 2 : 4;
+  const ifa::RowDtype dt = row_dtype(X);
+  const size_t elem = (size_t)ifa::row_elem_bytes(dt);
   int64_t dpad = d;
-  if (bf16) {
+  if (elem == 2) {
     while (dpad % 4 != 2) ++dpad;
   } else {
     while (dpad % 2 != 1) ++dpad;
@@ -555,7 +566,7 @@ torch::Tensor score_extended_sparse_v2(torch::Tensor X,
   TORCH_CHECK(lds <= 150 * 1024, "sparse v2 LDS overflow; use general path");
   int blocks = (int)std::min<int64_t>((N + 511) / 512, 8192);
   ifa::launch_score_extended_sparse_v2(
-      bf16, (int)nnz, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
+      dt, (int)nnz, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
       values.data_ptr<float>(), hidx.data_ptr<int32_t>(),
       hw.data_ptr<float>(), ncount.data_ptr<int32_t>(),
       out.data_ptr<float>(), N, (int32_t)d, (int32_t)dpad, (int32_t)T,
@@ -581,7 +592,7 @@ torch::Tensor score_forest_wide(torch::Tensor X, torch::Tensor nodes_wide,
   if (N == 0) return out;
   int blocks = (int)std::min<int64_t>((N + 255) / 256, 8192);
   ifa::launch_score_forest_wide(
-      is_bf16(X), X.data_ptr(), nodes_wide.data_ptr<int32_t>(),
+      row_dtype(X), X.data_ptr(), nodes_wide.data_ptr<int32_t>(),
       out.data_ptr<float>(), N, (int32_t)d, (int32_t)T, max_nodes,
       (int32_t)height_limit, (float)T, (float)c_norm, finalize ? 1 : 0,
       blocks, current_stream());
@@ -610,7 +621,7 @@ torch::Tensor score_extended_wide(torch::Tensor X, torch::Tensor nodes_wide,
   if (N == 0) return out;
   int blocks = (int)std::min<int64_t>((N + 255) / 256, 8192);
   ifa::launch_score_extended_wide(
-      is_bf16(X), X.data_ptr(), nodes_wide.data_ptr<int32_t>(),
+      row_dtype(X), X.data_ptr(), nodes_wide.data_ptr<int32_t>(),
       hidx.data_ptr<int32_t>(), hw.data_ptr<float>(), out.data_ptr<float>(),
       N, (int32_t)d, (int32_t)T, max_nodes, (int32_t)nnz, (float)T,
       (float)c_norm, finalize ? 1 : 0, blocks, current_stream());
@@ -647,13 +658,13 @@ torch::Tensor explain_forest(torch::Tensor X, torch::Tensor nodes_explain,
   const auto out_opts = X.options().dtype(torch::kFloat32);
   if (N == 0) return torch::empty({N, d}, out_opts);
 
-  const bool bf16 = is_bf16(X);
-  const size_t elem = bf16 ? 2 : 4;
+  const ifa::RowDtype dt = row_dtype(X);
+  const size_t elem = (size_t)ifa::row_elem_bytes(dt);
   const size_t budget = 150 * 1024;
   // odd-WORD strides (all LDS banks hit) with room for column d: the key
   // sentinel in the row tile, the self-loop sink in the accumulator tile
   int64_t dpad = d + 1;
-  if (bf16) {
+  if (elem == 2) {
     while (dpad % 4 != 2) ++dpad;
   } else {
     while (dpad % 2 != 1) ++dpad;
@@ -711,7 +722,7 @@ torch::Tensor explain_forest(torch::Tensor X, torch::Tensor nodes_explain,
   int blocks = (int)std::min<int64_t>(
       (N + rows_per_block - 1) / rows_per_block, max_blocks);
   ifa::launch_explain_forest(
-      bf16, mode, rpt, nodes_lds, X.data_ptr(),
+      dt, mode, rpt, nodes_lds, X.data_ptr(),
       nodes_explain.data_ptr<int32_t>(), ncount.data_ptr<int32_t>(),
       out.data_ptr<float>(), N, (int32_t)d, (int32_t)dpad, (int32_t)astride,
       (int32_t)T, (int32_t)max_nodes, (int32_t)tps, (int32_t)height_limit,
@@ -767,7 +778,7 @@ torch::Tensor explain_extended_forest(torch::Tensor X,
   }
   int blocks = (int)std::min<int64_t>((N + 255) / 256, max_blocks);
   ifa::launch_explain_extended(
-      is_bf16(X), X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
+      row_dtype(X), X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
       hidx.data_ptr<int32_t>(), hw.data_ptr<float>(), dl.data_ptr<float>(),
       dr.data_ptr<float>(), out.data_ptr<float>(), N, (int32_t)d, (int32_t)T,
       (int32_t)max_nodes, (int32_t)nnz, (float)T, finalize ? 1 : 0, blocks,

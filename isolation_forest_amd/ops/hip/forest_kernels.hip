@@ -52,6 +52,7 @@
 
 #include "det_math.h"
 #include "philox.h"
+#include "row_dtype.h"
 
 #define WAVE 64
 #define LANE_MASK_LT(lane) ((1ull << (lane)) - 1ull)
@@ -90,8 +91,22 @@ struct SegEntry {
 };
 
 // ---------------------------------------------------------------------------
-// bag gather: bags[T][n][d] (f32) <- X[N][d] (f32 or bf16) at idx[T][n]
+// bag gather: bags[T][n][d] (f32) <- X[N][d] (f32, bf16 or fp16) at idx[T][n]
 // ---------------------------------------------------------------------------
+
+// 16-bit rows come in two formats. uint16_t as the element/key type means
+// bf16 bits; f16_t is the DISTINCT type for IEEE fp16 bits (same size and
+// codegen as uint16_t, so every bf16 instantiation has an fp16 sibling that
+// differs only in the helpers below).
+enum class f16_t : uint16_t {};
+
+// fp16 -> f32, exact for every input (subnormals included: v_cvt_f32_f16
+// honours fp16 denormals, and every fp16 subnormal is a normal f32)
+__device__ __forceinline__ float f16_bits_to_f32(uint16_t b) {
+  union { uint16_t u; _Float16 h; } cv;
+  cv.u = b;
+  return (float)cv.h;
+}
 
 template <typename XT>
 __device__ __forceinline__ float load_feat(const XT* X, int64_t off);
@@ -105,6 +120,10 @@ __device__ __forceinline__ float load_feat<uint16_t>(const uint16_t* X, int64_t 
   union { uint32_t u; float f; } cv;
   cv.u = ((uint32_t)X[off]) << 16;  // bf16 -> f32 (exact)
   return cv.f;
+}
+template <>
+__device__ __forceinline__ float load_feat<f16_t>(const f16_t* X, int64_t off) {
+  return f16_bits_to_f32((uint16_t)X[off]);
 }
 
 template <typename XT>
@@ -493,6 +512,9 @@ __device__ __forceinline__ float cvt_feat(uint16_t v) {
   cv.u = ((uint32_t)v) << 16;
   return cv.f;
 }
+__device__ __forceinline__ float cvt_feat(f16_t v) {
+  return f16_bits_to_f32((uint16_t)v);
+}
 
 __device__ __forceinline__ int pn_feat(int meta) { return meta & 0xFFF; }
 __device__ __forceinline__ int pn_right(int meta) { return (meta >> 12) & 0x7FFF; }
@@ -507,6 +529,14 @@ __device__ __forceinline__ uint32_t key16(uint32_t b) {
   if (m > 0x7F80u) k = 0xFFFFu;
   return k;
 }
+// fp16 bits: same sign-magnitude fold, NaN is m > 0x7C00 (+inf -> 0xFC00)
+__device__ __forceinline__ uint32_t key16_f16(uint32_t b) {
+  const uint32_t m = b & 0x7FFFu;
+  uint32_t k = (b & 0x8000u) ? (0x7FFFu - m) : (0x8000u + m);
+  if (m == 0) k = 0x8000u;
+  if (m > 0x7C00u) k = 0xFFFFu;
+  return k;
+}
 __device__ __forceinline__ uint32_t key32(uint32_t b) {
   const uint32_t m = b & 0x7FFFFFFFu;
   uint32_t k = (b & 0x80000000u) ? (0x7FFFFFFFu - m) : (0x80000000u + m);
@@ -515,9 +545,13 @@ __device__ __forceinline__ uint32_t key32(uint32_t b) {
   return k;
 }
 
-// KT = uint16_t (bf16 input) or uint32_t (f32 input)
+// KT = uint16_t (bf16 input), f16_t (fp16 input) or uint32_t (f32 input)
 template <typename KT>
 __device__ __forceinline__ KT key_of_bits(KT b);
+template <>
+__device__ __forceinline__ f16_t key_of_bits<f16_t>(f16_t b) {
+  return (f16_t)(uint16_t)key16_f16((uint32_t)(uint16_t)b);
+}
 template <>
 __device__ __forceinline__ uint16_t key_of_bits<uint16_t>(uint16_t b) {
   return (uint16_t)key16((uint32_t)b);
@@ -533,19 +567,28 @@ __device__ __forceinline__ uint32_t key_of_bits<uint32_t>(uint32_t b) {
 __device__ __forceinline__ uint32_t widen_key(uint16_t k) {
   return ((uint32_t)k << 16) | 0xFFFFu;
 }
+__device__ __forceinline__ uint32_t widen_key(f16_t k) {
+  return widen_key((uint16_t)k);
+}
 __device__ __forceinline__ uint32_t widen_key(uint32_t k) { return k; }
+
+// all-ones key: the leaf sentinel column (and the NaN key)
+template <typename KT>
+__device__ __forceinline__ KT key_sentinel() { return (KT)~(KT)0; }
+template <>
+__device__ __forceinline__ f16_t key_sentinel<f16_t>() { return (f16_t)0xFFFFu; }
 
 // row stride in elements for the extended kernels: keep rows 16-B aligned
 template <typename XT>
 __device__ __host__ __forceinline__ int row_stride(int d) {
-  const int pad = 16 / (int)sizeof(XT);  // 8 for bf16, 4 for f32
+  const int pad = 16 / (int)sizeof(XT);  // 8 for bf16/fp16, 4 for f32
   return d + pad;
 }
 
 
 template <typename KT, int RPT, bool ROWS_LDS, int V4_ILP, bool NODES_LDS>
 __global__ void __launch_bounds__(256) score_forest_v4(
-    const KT* __restrict__ X,          // raw bf16/f32 bits [N][d]
+    const KT* __restrict__ X,          // raw bf16/fp16/f32 bits [N][d]
     const int2* __restrict__ nodes,    // [Tpad][max_nodes] packed v4
     const int32_t* __restrict__ ncnt,  // [Tpad]
     float* __restrict__ out,           // [N] (path sum or score)
@@ -569,7 +612,7 @@ __global__ void __launch_bounds__(256) score_forest_v4(
         rows[r * dpad + c] = key_of_bits<KT>(X[(block_row0 + r) * d + c]);
       }
       for (int r = tid; r < rows_per_iter; r += 256)
-        rows[r * dpad + d] = (KT)~(KT)0;  // leaf sentinel column
+        rows[r * dpad + d] = key_sentinel<KT>();  // leaf sentinel column
       __syncthreads();
     }
 
@@ -628,7 +671,7 @@ __global__ void __launch_bounds__(256) score_forest_v4(
               // global fallback: the sentinel column does not exist in X,
               // so guard the leaf feature index.
               const int64_t my_row = block_row0 + tid + r * 256;
-              kraw[r][s] = (f < d && my_row < N) ? X[my_row * d + f] : (KT)0;
+              kraw[r][s] = (f < d && my_row < N) ? X[my_row * d + f] : KT{};
             }
           }
         }
@@ -680,7 +723,7 @@ __global__ void __launch_bounds__(256) score_forest_v4(
 // extended scoring, dense fast path (nnz == d): per visit a dense dot
 // row[0..d) . w[0..d). WLDS stages the live tree's weight matrix in LDS
 // (L2 could not feed the ~17 TB/s the global-weight variant demanded);
-// rows are read as 8-byte vectors (4 bf16 or 2 f32 at a time).
+// rows are read as 8-byte vectors (4 bf16/fp16 or 2 f32 at a time).
 // Accumulation: 4 partial sums, pairwise combine (deterministic, not the
 // oracle's j-order — scoring parity tests use tolerance).
 // ---------------------------------------------------------------------------
@@ -694,6 +737,15 @@ __device__ __forceinline__ void row4(const uint16_t* p, int j4, float& x0,
   c.u = (v.y & 0xFFFFu) << 16;
   e.u = (v.y & 0xFFFF0000u);
   x0 = a.f; x1 = b.f; x2 = c.f; x3 = e.f;
+}
+
+__device__ __forceinline__ void row4(const f16_t* p, int j4, float& x0,
+                                     float& x1, float& x2, float& x3) {
+  const uint2 v = *(const uint2*)(p + 4 * j4);  // 8 B: 4 fp16
+  x0 = f16_bits_to_f32((uint16_t)(v.x & 0xFFFFu));
+  x1 = f16_bits_to_f32((uint16_t)(v.x >> 16));
+  x2 = f16_bits_to_f32((uint16_t)(v.y & 0xFFFFu));
+  x3 = f16_bits_to_f32((uint16_t)(v.y >> 16));
 }
 
 __device__ __forceinline__ void row4(const float* p, int j4, float& x0,
@@ -809,8 +861,13 @@ __global__ void __launch_bounds__(256) score_extended_dense_kernel(
 // bitwise; build stays bitwise).
 // ---------------------------------------------------------------------------
 
-template <typename KT>  // u16 = bf16 rows, u32 = f32 rows
+template <typename KT>  // u16 = bf16 rows, f16_t = fp16 rows, u32 = f32 rows
 __device__ __forceinline__ float load_row_f32(const KT* X, int64_t off);
+template <>
+__device__ __forceinline__ float load_row_f32<f16_t>(const f16_t* X,
+                                                     int64_t off) {
+  return f16_bits_to_f32((uint16_t)X[off]);
+}
 template <>
 __device__ __forceinline__ float load_row_f32<uint16_t>(const uint16_t* X,
                                                         int64_t off) {
@@ -825,7 +882,8 @@ __device__ __forceinline__ float load_row_f32<uint32_t>(const uint32_t* X,
 }
 
 // Row storage for the dense-EIF walk: rows are converted to f32 ONCE at
-// load (bf16->f32 is an exact shift) and held in registers across the
+// load (bf16->f32 is an exact shift, fp16->f32 an exact convert) and held
+// in registers across the
 // whole tree loop, so the dot needs zero per-visit unpack VALU. Register
 // budget: D=32 runs RPT=1 (32 row VGPRs), D<=16 runs RPT=2.
 template <typename KT, int D>
@@ -1130,6 +1188,9 @@ score_extended_dense_v3(
 __device__ __forceinline__ bool nonfinite_bits(uint16_t b) {
   return (b & 0x7F80u) == 0x7F80u;
 }
+__device__ __forceinline__ bool nonfinite_bits(f16_t b) {
+  return ((uint16_t)b & 0x7C00u) == 0x7C00u;
+}
 __device__ __forceinline__ bool nonfinite_bits(uint32_t b) {
   return (b & 0x7F800000u) == 0x7F800000u;
 }
@@ -1424,7 +1485,7 @@ __global__ void __launch_bounds__(256) score_extended_forest_kernel(
 
 template <typename KT>
 __global__ void __launch_bounds__(256) score_forest_wide(
-    const KT* __restrict__ X,          // raw bf16/f32 bits [N][d]
+    const KT* __restrict__ X,          // raw bf16/fp16/f32 bits [N][d]
     const int4* __restrict__ nodes,    // [T][max_nodes] {feat, right, w, 0}
     float* __restrict__ out, int64_t N, int32_t d, int32_t T,
     int64_t max_nodes, int32_t height_limit, float fT, float c_norm,
@@ -1537,7 +1598,7 @@ __device__ __forceinline__ float div32_exact(float a, float b) {
 
 template <typename KT, int RPT, bool ACC_LDS, bool ROWS_LDS, bool NODES_LDS>
 __global__ void __launch_bounds__(256) explain_forest_kernel(
-    const KT* __restrict__ X,          // raw bf16/f32 bits [N][d]
+    const KT* __restrict__ X,          // raw bf16/fp16/f32 bits [N][d]
     const int4* __restrict__ nodes,    // [T][max_nodes] explain records
     const int32_t* __restrict__ ncnt,  // [T]
     float* __restrict__ out,           // [N][d] (pre-zeroed when !ACC_LDS)
@@ -1563,7 +1624,7 @@ __global__ void __launch_bounds__(256) explain_forest_kernel(
         rows[r * dpad + c] = key_of_bits<KT>(X[(block_row0 + r) * d + c]);
       }
       for (int r = tid; r < rows_per_iter; r += 256)
-        rows[r * dpad + d] = (KT)~(KT)0;  // leaf sentinel column
+        rows[r * dpad + d] = key_sentinel<KT>();  // leaf sentinel column
     }
     if (ACC_LDS)
       for (int i = tid; i < rows_per_iter * astride; i += 256) acc[i] = 0.f;
@@ -1716,7 +1777,7 @@ static inline void raise_lds(const void* func, size_t bytes) {
                               (int)bytes);
 }
 
-void launch_bag_gather(bool bf16, const void* X, const int64_t* bag_idx,
+void launch_bag_gather(RowDtype dt, const void* X, const int64_t* bag_idx,
                        float* bags, int64_t T, int64_t n, int64_t d,
                        hipStream_t stream) {
   int64_t total = T * n * d;
@@ -1724,9 +1785,12 @@ void launch_bag_gather(bool bf16, const void* X, const int64_t* bag_idx,
   int blocks = (int)((total + threads - 1) / threads);
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
-  if (bf16)
+  if (dt == ROW_BF16)
     hipLaunchKernelGGL(bag_gather_kernel<uint16_t>, dim3(blocks), dim3(threads),
                        0, stream, (const uint16_t*)X, bag_idx, bags, T, n, d);
+  else if (dt == ROW_F16)
+    hipLaunchKernelGGL(bag_gather_kernel<f16_t>, dim3(blocks), dim3(threads),
+                       0, stream, (const f16_t*)X, bag_idx, bags, T, n, d);
   else
     hipLaunchKernelGGL(bag_gather_kernel<float>, dim3(blocks), dim3(threads), 0,
                        stream, (const float*)X, bag_idx, bags, T, n, d);
@@ -1764,7 +1828,7 @@ void launch_build_extended_forest(const float* bags, const int32_t* feat_sub,
                      n, d, k, nnz, max_nodes, height_limit);
 }
 
-void launch_score_forest(bool bf16, int rpt, bool rows_lds, bool nodes_lds,
+void launch_score_forest(RowDtype dt, int rpt, bool rows_lds, bool nodes_lds,
                          int ilp, const void* X, const void* nodes,
                          const int32_t* ncount, float* out, int64_t N,
                          int32_t d, int32_t dpad, int32_t Tpad,
@@ -1793,10 +1857,14 @@ void launch_score_forest(bool bf16, int rpt, bool rows_lds, bool nodes_lds,
     else if (ilp == 2) LS(KT, RPT, RL, 2);                                    \
     else LS(KT, RPT, RL, 4);                                                  \
   } while (0)
-  if (bf16) {
+  if (dt == ROW_BF16) {
     if (rows_lds && rpt == 2) LS_ILP(uint16_t, 2, true);
     else if (rows_lds) LS_ILP(uint16_t, 1, true);
     else LS_ILP(uint16_t, 1, false);
+  } else if (dt == ROW_F16) {
+    if (rows_lds && rpt == 2) LS_ILP(f16_t, 2, true);
+    else if (rows_lds) LS_ILP(f16_t, 1, true);
+    else LS_ILP(f16_t, 1, false);
   } else {
     if (rows_lds && rpt == 2) LS_ILP(uint32_t, 2, true);
     else if (rows_lds) LS_ILP(uint32_t, 1, true);
@@ -1806,7 +1874,7 @@ void launch_score_forest(bool bf16, int rpt, bool rows_lds, bool nodes_lds,
 #undef LS
 }
 
-void launch_score_extended_dense(bool bf16, bool rows_lds, bool wlds,
+void launch_score_extended_dense(RowDtype dt, bool rows_lds, bool wlds,
                                  const void* X, const void* nodes,
                                  const float* hw, const int32_t* ncount,
                                  float* out, int64_t N, int32_t d,
@@ -1821,11 +1889,16 @@ void launch_score_extended_dense(bool bf16, bool rows_lds, bool wlds,
                        (const int2*)nodes, hw, ncount, out, N, d, dpad, T,    \
                        max_nodes, fT, c_norm, finalize);                      \
   } while (0)
-  if (bf16) {
+  if (dt == ROW_BF16) {
     if (rows_lds && wlds) LSD(uint16_t, true, true);
     else if (rows_lds) LSD(uint16_t, true, false);
     else if (wlds) LSD(uint16_t, false, true);
     else LSD(uint16_t, false, false);
+  } else if (dt == ROW_F16) {
+    if (rows_lds && wlds) LSD(f16_t, true, true);
+    else if (rows_lds) LSD(f16_t, true, false);
+    else if (wlds) LSD(f16_t, false, true);
+    else LSD(f16_t, false, false);
   } else {
     if (rows_lds && wlds) LSD(float, true, true);
     else if (rows_lds) LSD(float, true, false);
@@ -1835,7 +1908,7 @@ void launch_score_extended_dense(bool bf16, bool rows_lds, bool wlds,
 #undef LSD
 }
 
-void launch_score_extended_dense_v2(bool bf16, int D, const void* X,
+void launch_score_extended_dense_v2(RowDtype dt, int D, const void* X,
                                     const void* nodes, const float* values,
                                     const float* hw, const int32_t* ncount,
                                     float* out, int64_t N, int32_t d,
@@ -1853,11 +1926,16 @@ void launch_score_extended_dense_v2(bool bf16, int D, const void* X,
   } while (0)
   // D=32 runs RPT=1: 2 rows/thread would spill past the 128-VGPR budget
   // that keeps 4 waves/SIMD resident (2 blocks/CU at ~80 KB LDS each)
-  if (bf16) {
+  if (dt == ROW_BF16) {
     if (D == 8) LSD2(uint16_t, 8, 2);
     else if (D == 16) LSD2(uint16_t, 16, 2);
     else if (D == 64) LSD2(uint16_t, 64, 1);
     else LSD2(uint16_t, 32, 1);
+  } else if (dt == ROW_F16) {
+    if (D == 8) LSD2(f16_t, 8, 2);
+    else if (D == 16) LSD2(f16_t, 16, 2);
+    else if (D == 64) LSD2(f16_t, 64, 1);
+    else LSD2(f16_t, 32, 1);
   } else {
     if (D == 8) LSD2(uint32_t, 8, 2);
     else if (D == 16) LSD2(uint32_t, 16, 2);
@@ -1867,14 +1945,18 @@ void launch_score_extended_dense_v2(bool bf16, int D, const void* X,
 #undef LSD2
 }
 
-void launch_score_forest_wide(bool bf16, const void* X, const void* nodes,
+void launch_score_forest_wide(RowDtype dt, const void* X, const void* nodes,
                               float* out, int64_t N, int32_t d, int32_t T,
                               int64_t max_nodes, int32_t height_limit,
                               float fT, float c_norm, int finalize,
                               int blocks, hipStream_t stream) {
-  if (bf16)
+  if (dt == ROW_BF16)
     hipLaunchKernelGGL((score_forest_wide<uint16_t>), dim3(blocks), dim3(256),
                        0, stream, (const uint16_t*)X, (const int4*)nodes, out,
+                       N, d, T, max_nodes, height_limit, fT, c_norm, finalize);
+  else if (dt == ROW_F16)
+    hipLaunchKernelGGL((score_forest_wide<f16_t>), dim3(blocks), dim3(256),
+                       0, stream, (const f16_t*)X, (const int4*)nodes, out,
                        N, d, T, max_nodes, height_limit, fT, c_norm, finalize);
   else
     hipLaunchKernelGGL((score_forest_wide<uint32_t>), dim3(blocks), dim3(256),
@@ -1882,15 +1964,20 @@ void launch_score_forest_wide(bool bf16, const void* X, const void* nodes,
                        N, d, T, max_nodes, height_limit, fT, c_norm, finalize);
 }
 
-void launch_score_extended_wide(bool bf16, const void* X, const void* nodes,
+void launch_score_extended_wide(RowDtype dt, const void* X, const void* nodes,
                                 const int32_t* hidx, const float* hw,
                                 float* out, int64_t N, int32_t d, int32_t T,
                                 int64_t max_nodes, int32_t nnz, float fT,
                                 float c_norm, int finalize, int blocks,
                                 hipStream_t stream) {
-  if (bf16)
+  if (dt == ROW_BF16)
     hipLaunchKernelGGL((score_extended_wide<uint16_t>), dim3(blocks),
                        dim3(256), 0, stream, (const uint16_t*)X,
+                       (const int4*)nodes, hidx, hw, out, N, d, T, max_nodes,
+                       nnz, fT, c_norm, finalize);
+  else if (dt == ROW_F16)
+    hipLaunchKernelGGL((score_extended_wide<f16_t>), dim3(blocks),
+                       dim3(256), 0, stream, (const f16_t*)X,
                        (const int4*)nodes, hidx, hw, out, N, d, T, max_nodes,
                        nnz, fT, c_norm, finalize);
   else
@@ -1927,7 +2014,7 @@ void launch_score_extended_dense_v3(int D, bool rpt2, const void* X,
 }
 
 void launch_score_extended_dense_nonfinite_rows(
-    bool bf16, bool packed_w, const void* X, const void* nodes,
+    RowDtype dt, bool packed_w, const void* X, const void* nodes,
     const float* values, const void* wts, float* out, int64_t N, int32_t d,
     int32_t D, int32_t T, int32_t max_nodes, int32_t height_limit, float fT,
     float c_norm, int finalize, int blocks, hipStream_t stream) {
@@ -1936,15 +2023,18 @@ void launch_score_extended_dense_nonfinite_rows(
                      dim3(blocks), dim3(256), 0, stream, (const KT*)X,        \
                      (const int2*)nodes, values, wts, out, N, d, D, T,        \
                      max_nodes, height_limit, fT, c_norm, finalize)
-  if (bf16) {
+  // v3 (packed weights) takes bf16 rows only
+  if (dt == ROW_BF16) {
     if (packed_w) LNF(uint16_t, true); else LNF(uint16_t, false);
+  } else if (dt == ROW_F16) {
+    LNF(f16_t, false);
   } else {
-    LNF(uint32_t, false);  // v3 (packed weights) takes bf16 rows only
+    LNF(uint32_t, false);
   }
 #undef LNF
 }
 
-void launch_score_extended_sparse_v2(bool bf16, int nnz, const void* X,
+void launch_score_extended_sparse_v2(RowDtype dt, int nnz, const void* X,
                                      const void* nodes, const float* values,
                                      const int32_t* hidx, const float* hw,
                                      const int32_t* ncount, float* out,
@@ -1972,12 +2062,14 @@ void launch_score_extended_sparse_v2(bool bf16, int nnz, const void* X,
       default: LSS2(KT, 5); break;                                            \
     }                                                                         \
   } while (0)
-  if (bf16) LSS2_ALL(uint16_t); else LSS2_ALL(uint32_t);
+  if (dt == ROW_BF16) LSS2_ALL(uint16_t);
+  else if (dt == ROW_F16) LSS2_ALL(f16_t);
+  else LSS2_ALL(uint32_t);
 #undef LSS2_ALL
 #undef LSS2
 }
 
-void launch_score_extended_forest(bool bf16, bool rows_lds, bool hyper_lds,
+void launch_score_extended_forest(RowDtype dt, bool rows_lds, bool hyper_lds,
                                   bool nodes_lds, const void* X,
                                   const void* nodes, const int32_t* hidx,
                                   const float* hw, const int32_t* ncount,
@@ -2003,11 +2095,16 @@ void launch_score_extended_forest(bool bf16, bool rows_lds, bool hyper_lds,
                          max_nodes, nnz, fT, c_norm, finalize);               \
     }                                                                         \
   } while (0)
-  if (bf16) {
+  if (dt == ROW_BF16) {
     if (rows_lds && hyper_lds) LSE(uint16_t, true, true);
     else if (rows_lds) LSE(uint16_t, true, false);
     else if (hyper_lds) LSE(uint16_t, false, true);
     else LSE(uint16_t, false, false);
+  } else if (dt == ROW_F16) {
+    if (rows_lds && hyper_lds) LSE(f16_t, true, true);
+    else if (rows_lds) LSE(f16_t, true, false);
+    else if (hyper_lds) LSE(f16_t, false, true);
+    else LSE(f16_t, false, false);
   } else {
     if (rows_lds && hyper_lds) LSE(float, true, true);
     else if (rows_lds) LSE(float, true, false);
@@ -2019,7 +2116,7 @@ void launch_score_extended_forest(bool bf16, bool rows_lds, bool hyper_lds,
 
 // mode: 0 = accumulators + rows in LDS (rpt 1 or 2), 1 = global
 // accumulators with rows in LDS, 2 = global accumulators and global rows
-void launch_explain_forest(bool bf16, int mode, int rpt, bool nodes_lds,
+void launch_explain_forest(RowDtype dt, int mode, int rpt, bool nodes_lds,
                            const void* X, const void* nodes,
                            const int32_t* ncount, float* out, int64_t N,
                            int32_t d, int32_t dpad, int32_t astride,
@@ -2041,8 +2138,10 @@ void launch_explain_forest(bool bf16, int mode, int rpt, bool nodes_lds,
     else if (mode == 1) LX(KT, 1, false, true, NL);                           \
     else LX(KT, 1, false, false, NL);                                         \
   } while (0)
-  if (bf16) {
+  if (dt == ROW_BF16) {
     if (nodes_lds) LX_MODE(uint16_t, true); else LX_MODE(uint16_t, false);
+  } else if (dt == ROW_F16) {
+    if (nodes_lds) LX_MODE(f16_t, true); else LX_MODE(f16_t, false);
   } else {
     if (nodes_lds) LX_MODE(uint32_t, true); else LX_MODE(uint32_t, false);
   }
@@ -2050,15 +2149,20 @@ void launch_explain_forest(bool bf16, int mode, int rpt, bool nodes_lds,
 #undef LX
 }
 
-void launch_explain_extended(bool bf16, const void* X, const void* nodes,
+void launch_explain_extended(RowDtype dt, const void* X, const void* nodes,
                              const int32_t* hidx, const float* hw,
                              const float* dl, const float* dr, float* out,
                              int64_t N, int32_t d, int32_t T,
                              int32_t max_nodes, int32_t nnz, float fT,
                              int finalize, int blocks, hipStream_t stream) {
-  if (bf16)
+  if (dt == ROW_BF16)
     hipLaunchKernelGGL((explain_extended_kernel<uint16_t>), dim3(blocks),
                        dim3(256), 0, stream, (const uint16_t*)X,
+                       (const int2*)nodes, hidx, hw, dl, dr, out, N, d, T,
+                       max_nodes, nnz, fT, finalize);
+  else if (dt == ROW_F16)
+    hipLaunchKernelGGL((explain_extended_kernel<f16_t>), dim3(blocks),
+                       dim3(256), 0, stream, (const f16_t*)X,
                        (const int2*)nodes, hidx, hw, dl, dr, out, N, d, T,
                        max_nodes, nnz, fT, finalize);
   else

@@ -35,7 +35,7 @@ def main():
     ap.add_argument("--features", type=int, default=32)
     ap.add_argument("--trees", type=int, default=1000)
     ap.add_argument("--max-samples", type=int, default=256)
-    ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
+    ap.add_argument("--dtype", choices=["bf16", "fp16", "fp32"], default="bf16")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--extended", action="store_true")
@@ -51,7 +51,8 @@ def main():
     dev = "cuda:0"
     g = torch.Generator(device=dev)
     g.manual_seed(7)
-    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+    dtype = {"bf16": torch.bfloat16, "fp16": torch.float16,
+             "fp32": torch.float32}[args.dtype]
     X = torch.randn((args.rows, args.features), device=dev,
                     generator=g).to(dtype)
 

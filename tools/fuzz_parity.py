@@ -2,8 +2,8 @@
 """Differential GPU<->CPU fuzzer.
 
 Random configurations of (rows, features, subsampling, tree count,
-extension level, dtype, bootstrap, data pathologies): build on the GPU and
-on the CPU oracle, demand BITWISE forest equality; score on both, demand
+extension level, row dtype f32/bf16/fp16, bootstrap, data pathologies):
+build on the GPU and on the CPU oracle (which sees the upcast matrix), demand BITWISE forest equality; score on both, demand
 the routing contract (bitwise for standard/sparse walks, knife-edge
 tolerance for reassociated dense dots). Exits non-zero on the first
 divergence with a repro line.
@@ -59,7 +59,9 @@ def one_case(rs: np.random.RandomState, it: int) -> str:
     T = int(rs.choice([1, 2, 3, 7, 8, 16, 33]))
     seed = int(rs.randint(1, 2**30))
     extended = bool(rs.randint(0, 2))
-    bf16 = bool(rs.randint(0, 2))
+    rowdt = ("f32", "bf16", "f16")[int(rs.randint(0, 3))]
+    bf16 = rowdt == "bf16"
+    half = rowdt != "f32"  # 2-byte rows: bf16 or fp16
     bootstrap = bool(rs.randint(0, 2))
     patho = rs.choice(["normal", "const_col", "dups", "big", "tiny"])
 
@@ -69,16 +71,19 @@ def one_case(rs: np.random.RandomState, it: int) -> str:
     elif patho == "dups":
         X = X[rs.randint(0, max(rows // 7, 1), size=rows)]
     elif patho == "big":
-        X *= 1e20
+        # fp16 tops out at 65504: stay in range (inf rows would make the
+        # build's min/max scan degenerate, which is not what this draws for)
+        X *= 1e4 if rowdt == "f16" else 1e20
     elif patho == "tiny":
-        X *= 1e-20
+        # fp16: mostly subnormals (|x| < 2^-14), multiples of 2^-24
+        X *= 1e-5 if rowdt == "f16" else 1e-20
     desc = (f"it={it} rows={rows} d={d} n={n} k={k} T={T} seed={seed} "
-            f"ext={extended} bf16={bf16} boot={bootstrap} patho={patho}")
+            f"ext={extended} dtype={rowdt} boot={bootstrap} patho={patho}")
 
     Xt = torch.from_numpy(X).to("cuda")
-    if bf16:
-        Xt = Xt.to(torch.bfloat16)
-        X = Xt.float().cpu().numpy()
+    if half:
+        Xt = Xt.to(torch.bfloat16 if bf16 else torch.float16)
+        X = Xt.float().cpu().numpy()  # exact upcast: what the kernels see
 
     bag = cpu_engine.sample_bags(rows, T, n, seed=seed, bootstrap=bootstrap)
     fs = cpu_engine.feature_subsets(d, k, T, seed=seed)
@@ -132,9 +137,9 @@ def one_case(rs: np.random.RandomState, it: int) -> str:
         # general kernel keep strict j-order (bitwise); dense reassociates
         nnz = min(ext_level + 1, k)
         mn = gpu_f.feature.shape[1]
-        elem = 2 if bf16 else 4
+        elem = 2 if half else 4
         dpad_s = d
-        while (dpad_s % 4 != 2) if bf16 else (dpad_s % 2 != 1):
+        while (dpad_s % 4 != 2) if half else (dpad_s % 2 != 1):
             dpad_s += 1
         sparse_route = (nnz <= 5
                         and mn * (12 + nnz * 8) + 2 * 256 * dpad_s * elem
@@ -149,7 +154,8 @@ def one_case(rs: np.random.RandomState, it: int) -> str:
             D = 64
         else:
             D = 128
-        d_cap = 128 if bf16 else 64  # v3 packs bf16 weights; v2 f32
+        # v3 (bf16 rows only) packs bf16 weights; f32 and fp16 rows take v2
+        d_cap = 128 if bf16 else 64
         wbytes = (D // 8 + 1) * 16 if bf16 else (D // 4 + 1) * 16
         dense_route = (not sparse_route and d <= d_cap
                        and (nnz == d or nnz >= 6)

@@ -7,9 +7,10 @@
 // which is torch-free) over a raw row-major matrix.
 //
 //   ifa_score <model_dir> <input.bin> <rows> <features> <scores_out.bin>
-//             [--bf16] [--labels labels_out.bin]
+//             [--bf16 | --f16] [--labels labels_out.bin]
 //
-// input.bin: rows*features little-endian f32 (or bf16 with --bf16).
+// input.bin: rows*features little-endian f32 (bf16 with --bf16, IEEE fp16
+// with --f16).
 // scores_out.bin: rows f32 outlier scores. --labels: rows u8 (score >=
 // outlierScoreThreshold), requires a threshold-bearing model.
 //
@@ -41,15 +42,17 @@
 #include <string>
 #include <vector>
 
+#include "row_dtype.h"
+
 namespace ifa {
-void launch_score_forest(bool bf16, int rpt, bool rows_lds, bool nodes_lds,
+void launch_score_forest(RowDtype dt, int rpt, bool rows_lds, bool nodes_lds,
                          int ilp, const void* X, const void* nodes,
                          const int32_t* ncount, float* out, int64_t N,
                          int32_t d, int32_t dpad, int32_t Tpad,
                          int32_t max_nodes, int32_t height_limit, float fT,
                          float c_norm, int finalize, size_t lds, int blocks,
                          hipStream_t stream);
-void launch_score_extended_dense_v2(bool bf16, int D, const void* X,
+void launch_score_extended_dense_v2(RowDtype dt, int D, const void* X,
                                     const void* nodes, const float* values,
                                     const float* hw, const int32_t* ncount,
                                     float* out, int64_t N, int32_t d,
@@ -57,7 +60,7 @@ void launch_score_extended_dense_v2(bool bf16, int D, const void* X,
                                     int32_t height_limit, float fT,
                                     float c_norm, int finalize, size_t lds,
                                     int blocks, hipStream_t stream);
-void launch_score_extended_sparse_v2(bool bf16, int nnz, const void* X,
+void launch_score_extended_sparse_v2(RowDtype dt, int nnz, const void* X,
                                      const void* nodes, const float* values,
                                      const int32_t* hidx, const float* hw,
                                      const int32_t* ncount, float* out,
@@ -369,6 +372,41 @@ static uint32_t bf16_threshold_key(float s) {
   return k << 16;
 }
 
+// Smallest producible fp16 key whose value is >= s, in the high 16 bits
+// (mirror of ops/gpu_engine._f16_threshold_keys). ceil16(s) is computed by
+// stepping over exact fp16 values: convert RTZ via the bit layout, then bump
+// toward +inf when the conversion lost anything.
+static float f16_bits_value(uint32_t h) {
+  const uint32_t e = (h >> 10) & 0x1Fu, f = h & 0x3FFu;
+  float v;
+  if (e == 0) v = ldexpf((float)f, -24);
+  else if (e == 31) v = f ? NAN : INFINITY;
+  else v = ldexpf((float)(f | 0x400u), (int)e - 25);
+  return (h & 0x8000u) ? -v : v;
+}
+
+static uint32_t f16_threshold_key(float s) {
+  // magnitude bits of the largest fp16 with |value| <= |s| (0x7C00 = inf)
+  const float a = fabsf(s);
+  uint32_t lo = 0, hi = 0x7C00u;  // invariant: value(lo) <= a
+  while (lo < hi) {               // 15 steps over the ordered magnitudes
+    const uint32_t mid = (lo + hi + 1) / 2;
+    if (f16_bits_value(mid) <= a) lo = mid; else hi = mid - 1;
+  }
+  const bool exact = f16_bits_value(lo) == a;
+  uint32_t k;
+  if (s > 0.0f) {
+    const uint32_t mm = exact ? lo : lo + 1;  // round up in magnitude
+    k = 0x8000u + mm;
+  } else if (s < 0.0f) {
+    const uint32_t mm = lo;  // toward +inf = down in magnitude
+    k = mm == 0 ? 0x8000u : 0x7FFFu - mm;
+  } else {
+    k = 0x8000u;
+  }
+  return k << 16;
+}
+
 static uint32_t f32_key(float s) {
   uint32_t b;
   memcpy(&b, &s, 4);
@@ -384,7 +422,7 @@ struct Packed {
   int Tpad = 0, T = 0, mn = 0, max_depth = 1;
 };
 
-static Packed pack_v4(const Model& m, int d_sentinel, bool bf16) {
+static Packed pack_v4(const Model& m, int d_sentinel, ifa::RowDtype dt) {
   Packed p;
   p.T = m.trees.empty() ? 0 : (m.trees.rbegin()->first + 1);
   for (const auto& kv : m.trees)
@@ -436,7 +474,9 @@ static Packed pack_v4(const Model& m, int d_sentinel, bool bf16) {
         float s32 = (float)nd.split_value;
         if ((double)s32 < nd.split_value)
           s32 = std::nextafterf(s32, INFINITY);
-        uint32_t key = bf16 ? bf16_threshold_key(s32) : f32_key(s32);
+        uint32_t key = dt == ifa::ROW_BF16  ? bf16_threshold_key(s32)
+                       : dt == ifa::ROW_F16 ? f16_threshold_key(s32)
+                                            : f32_key(s32);
         memcpy(&w1, &key, 4);
         p.max_depth = std::max(p.max_depth, depth.at(nd.id) + 1);
       }
@@ -537,17 +577,18 @@ int main(int argc, char** argv) {
   if (argc < 6) {
     fprintf(stderr,
             "usage: %s <model_dir> <input.bin> <rows> <features> "
-            "<scores_out.bin> [--bf16] [--labels labels_out.bin]\n",
+            "<scores_out.bin> [--bf16 | --f16] [--labels labels_out.bin]\n",
             argv[0]);
     return 2;
   }
   std::string model_dir = argv[1], input = argv[2], out_path = argv[5];
   int64_t N = atoll(argv[3]);
   int d = atoi(argv[4]);
-  bool bf16 = false;
+  ifa::RowDtype dt = ifa::ROW_F32;
   std::string labels_path;
   for (int i = 6; i < argc; ++i) {
-    if (!strcmp(argv[i], "--bf16")) bf16 = true;
+    if (!strcmp(argv[i], "--bf16")) dt = ifa::ROW_BF16;
+    else if (!strcmp(argv[i], "--f16")) dt = ifa::ROW_F16;
     else if (!strcmp(argv[i], "--labels") && i + 1 < argc)
       labels_path = argv[++i];
   }
@@ -579,7 +620,8 @@ int main(int argc, char** argv) {
   }
   float c_norm = avg_path_length32(m.num_samples);
 
-  size_t elem = bf16 ? 2 : 4;
+  size_t elem = (size_t)ifa::row_elem_bytes(dt);
+  const bool half_rows = elem == 2;  // bf16 or fp16: 2-byte LDS strides
   auto data = read_file(input);
   if (data.size() != (size_t)N * d * elem) {
     fprintf(stderr, "error: %s is %zu bytes, expected %zu (N*d*%zu)\n",
@@ -594,7 +636,7 @@ int main(int argc, char** argv) {
 
   const size_t kMaxLds = 160 * 1024;
   int64_t dpad = d + 1;
-  if (bf16) {
+  if (half_rows) {
     while (dpad % 4 != 2) ++dpad;
   } else {
     while (dpad % 2 != 1) ++dpad;
@@ -602,7 +644,7 @@ int main(int argc, char** argv) {
   int T_report = 0;
 
   if (!m.extended) {
-    Packed p = pack_v4(m, d, bf16);
+    Packed p = pack_v4(m, d, dt);
     T_report = p.T;
     void *dNodes, *dNcount;
     HIP_CHECK(hipMalloc(&dNodes, p.nodes.size() * 4));
@@ -632,7 +674,7 @@ int main(int argc, char** argv) {
     int64_t rows_per_block = (int64_t)(rows_lds ? rpt : 1) * 256;
     int blocks = (int)std::min<int64_t>(
         (N + rows_per_block - 1) / rows_per_block, 8192);
-    ifa::launch_score_forest(bf16, rpt, rows_lds, nodes_lds, 4, dX, dNodes,
+    ifa::launch_score_forest(dt, rpt, rows_lds, nodes_lds, 4, dX, dNodes,
                              (const int32_t*)dNcount, (float*)dOut, N, d,
                              (int32_t)dpad, p.Tpad, p.mn, p.max_depth,
                              (float)p.T, c_norm, 1, lds, blocks, 0);
@@ -668,10 +710,10 @@ int main(int argc, char** argv) {
         HIP_CHECK(hipMemcpy(dNcount, p.ncount.data(), p.ncount.size() * 4,
                             hipMemcpyHostToDevice));
         int64_t dpad_s = d;  // sparse kernel stride (no sentinel column)
-        if (bf16) { while (dpad_s % 4 != 2) ++dpad_s; }
+        if (half_rows) { while (dpad_s % 4 != 2) ++dpad_s; }
         else { while (dpad_s % 2 != 1) ++dpad_s; }
         ifa::launch_score_extended_sparse_v2(
-            bf16, p.nnz, dX, dNodes, (const float*)dVals,
+            dt, p.nnz, dX, dNodes, (const float*)dVals,
             (const int32_t*)dHidx, (const float*)dHw,
             (const int32_t*)dNcount, (float*)dOut, N, d, (int32_t)dpad_s,
             p.T, p.mn, p.max_depth, (float)p.T, c_norm, 1, lds, blocks, 0);
@@ -710,7 +752,7 @@ int main(int argc, char** argv) {
       HIP_CHECK(hipMemcpy(dNcount, p.ncount.data(), p.ncount.size() * 4,
                           hipMemcpyHostToDevice));
       ifa::launch_score_extended_dense_v2(
-          bf16, D, dX, dNodes, (const float*)dVals, (const float*)dHw,
+          dt, D, dX, dNodes, (const float*)dVals, (const float*)dHw,
           (const int32_t*)dNcount, (float*)dOut, N, d, p.T, p.mn,
           p.max_depth, (float)p.T, c_norm, 1, lds, blocks, 0);
     }
@@ -745,6 +787,7 @@ launched:
   fprintf(stderr,
           "scored %lld rows x %d trees (%s%s); threshold=%.6f flagged=%lld\n",
           (long long)N, T_report, m.extended ? "extended, " : "",
-          bf16 ? "bf16" : "f32", m.threshold, (long long)flagged);
+          dt == ifa::ROW_BF16 ? "bf16" : (dt == ifa::ROW_F16 ? "f16" : "f32"),
+          m.threshold, (long long)flagged);
   return 0;
 }
