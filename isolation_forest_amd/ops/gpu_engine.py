@@ -845,6 +845,19 @@ def _eif_dense_packed_device(raw, D: int):
     return packed, values, hw_dense, max_depth
 
 
+def _v4_walk_order(aos: torch.Tensor, ncount: torch.Tensor) -> torch.Tensor:
+    """Pre-order v4 records (what the four packers emit) -> the level-order
+    records score_forest_v4 walks (link = right child, left = link - 1);
+    one small kernel per pack, cached with it. Part of packing, like the
+    torch-side packers, not a scoring route: the extension is taken from the
+    package, so a routing proxy installed on this module sees scoring calls
+    only."""
+    from . import load_extension as _packing_extension
+
+    return _packing_extension().v4_level_order(aos.contiguous(),
+                                               ncount.contiguous())
+
+
 def _device_forest(model, device, v4_key=None):
     """Cached device copy of the packed forest. v4_key = (d, kind) selects
     the standard-scoring v4 packing; None = the EIF packing. Packs that
@@ -936,8 +949,8 @@ def _device_forest(model, device, v4_key=None):
         elif isinstance(v4_key, tuple) and v4_key[0] == "eif0":
             packed, ncount_np, max_depth = _eif0_packed_v4(
                 forest, v4_key[1], v4_key[2])
-            aos = torch.from_numpy(packed).to(device)
             ncount = torch.from_numpy(ncount_np).to(device)
+            aos = _v4_walk_order(torch.from_numpy(packed).to(device), ncount)
             extra["height"] = max_depth
         elif isinstance(v4_key, tuple) and v4_key[0] == "explain":
             packed, max_depth = _nodes_packed_explain(
@@ -987,6 +1000,7 @@ def _device_forest(model, device, v4_key=None):
                 packed, ncount_np, max_depth = _nodes_packed_v4(forest, d, kind)
                 aos = torch.from_numpy(packed).to(device)
                 ncount = torch.from_numpy(ncount_np).to(device)
+            aos = _v4_walk_order(aos, ncount)
             extra["height"] = max_depth
         else:
             aos = torch.from_numpy(_nodes_packed(forest)).to(device)

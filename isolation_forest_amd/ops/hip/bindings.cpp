@@ -35,10 +35,14 @@ void launch_build_extended_forest(const float* bags, const int32_t* feat_sub,
                                   int32_t max_nodes, int32_t height_limit,
                                   size_t lds, hipStream_t stream);
 
+void launch_v4_level_order(const void* nodes, const int32_t* ncount,
+                           void* out, int32_t Tpad, int32_t max_nodes,
+                           hipStream_t stream);
+
 void launch_score_forest(RowDtype dt, int rpt, bool rows_lds, bool nodes_lds,
                          int ilp, const void* X, const void* nodes,
                          const int32_t* ncount, float* out, int64_t N,
-                         int32_t d, int32_t dpad, int32_t Tpad,
+                         int32_t d, int32_t Tpad,
                          int32_t max_nodes, int32_t height_limit, float fT,
                          float c_norm, int finalize, size_t lds, int blocks,
                          hipStream_t stream);
@@ -257,6 +261,32 @@ std::vector<torch::Tensor> build_extended_forest(
   return {feat, value, right, count, ncount, hidx, hw, off64, depth};
 }
 
+// pre-order v4 records (what the packers emit) -> the level-order records
+// score_forest walks; see v4_level_order_kernel
+torch::Tensor v4_level_order(torch::Tensor nodes_packed,
+                             torch::Tensor ncount) {
+  CHECK_CUDA(nodes_packed);
+  CHECK_CONTIG(nodes_packed);
+  CHECK_CUDA(ncount);
+  CHECK_CONTIG(ncount);
+  TORCH_CHECK(nodes_packed.dim() == 3 && nodes_packed.size(2) == 2 &&
+                  nodes_packed.scalar_type() == torch::kInt32,
+              "nodes must be packed int32 [Tpad, max_nodes, 2]");
+  TORCH_CHECK(ncount.scalar_type() == torch::kInt32 && ncount.dim() == 1 &&
+                  ncount.size(0) == nodes_packed.size(0),
+              "ncount must be int32 [Tpad]");
+  TORCH_CHECK(nodes_packed.size(1) >= 1 && nodes_packed.size(1) <= 32767,
+              "packed node ids are 15 bits");
+  auto out = torch::empty_like(nodes_packed);
+  if (nodes_packed.size(0) == 0) return out;
+  ifa::launch_v4_level_order(nodes_packed.data_ptr<int32_t>(),
+                             ncount.data_ptr<int32_t>(),
+                             out.data_ptr<int32_t>(),
+                             (int32_t)nodes_packed.size(0),
+                             (int32_t)nodes_packed.size(1), current_stream());
+  return out;
+}
+
 torch::Tensor score_forest(torch::Tensor X, torch::Tensor nodes_packed,
                            torch::Tensor ncount, int64_t num_trees,
                            int64_t height_limit, double c_norm,
@@ -284,18 +314,13 @@ torch::Tensor score_forest(torch::Tensor X, torch::Tensor nodes_packed,
 
   const ifa::RowDtype dt = row_dtype(X);
   const size_t elem = (size_t)ifa::row_elem_bytes(dt);
-  // odd-WORD row stride (all 32 LDS banks hit) with room for the sentinel
-  // column at index d
-  int64_t dpad = d + 1;
-  if (elem == 2) {
-    while (dpad % 4 != 2) ++dpad;  // dpad u16 elems -> dpad/2 words, odd
-  } else {
-    while (dpad % 2 != 1) ++dpad;  // odd word count
-  }
+  // feature-major key tile: d feature slabs plus the sentinel slab, each
+  // rows_per_block keys, lane-adjacent — no padding needed
+  const int64_t slabs = d + 1;
   // deep forests (large maxSamples) overflow LDS node staging: walk nodes
   // from global/L2 instead (NODES_LDS=false) — correct for any tree size
   bool nodes_lds =
-      (size_t)2 * max_nodes * 8 + (size_t)256 * dpad * elem <= 150 * 1024;
+      (size_t)2 * max_nodes * 8 + (size_t)256 * slabs * elem <= 150 * 1024;
   // config search over (rpt, ilp): wide-d rows inflate the LDS row tile,
   // so dropping staged-tree ILP to 2 can buy back a resident block
   // (measured: d=128 went 1 block/CU at ILP=4 -> 124M rows/s; ILP=2 at 2
@@ -311,7 +336,7 @@ torch::Tensor score_forest(torch::Tensor X, torch::Tensor nodes_packed,
     bool found = false;
     for (const Cand& cnd : cands) {
       size_t nb = nodes_lds ? (size_t)cnd.ilp * max_nodes * 8 : 0;
-      size_t l = nb + (size_t)cnd.rpt * 256 * dpad * elem;
+      size_t l = nb + (size_t)cnd.rpt * 256 * slabs * elem;
       if (l > 150 * 1024) continue;
       int blocks_cu = (int)std::min<size_t>(kMaxLds / std::max(l, (size_t)1),
                                             3);
@@ -345,7 +370,7 @@ torch::Tensor score_forest(torch::Tensor X, torch::Tensor nodes_packed,
   ifa::launch_score_forest(dt, rpt, rows_lds, nodes_lds, ilp, X.data_ptr(),
                            nodes_packed.data_ptr<int32_t>(),
                            ncount.data_ptr<int32_t>(), out.data_ptr<float>(),
-                           N, (int32_t)d, (int32_t)dpad, (int32_t)Tpad,
+                           N, (int32_t)d, (int32_t)Tpad,
                            (int32_t)max_nodes, (int32_t)height_limit,
                            (float)num_trees, (float)c_norm, finalize ? 1 : 0,
                            lds, blocks, current_stream());
@@ -791,6 +816,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("build_forest", &build_forest, "build standard iTrees (K1/K2/K11)");
   m.def("build_extended_forest", &build_extended_forest,
         "build extended iTrees (K3-K5)");
+  m.def("v4_level_order", &v4_level_order,
+        "re-lay pre-order v4 node records in level order for score_forest");
   m.def("score_forest", &score_forest, "batched path-length scoring (K6)");
   m.def("score_extended_forest", &score_extended_forest,
         "batched EIF scoring (K7)");

@@ -487,7 +487,9 @@ __global__ void __launch_bounds__(WAVE) build_extended_forest_kernel(
 // ---------------------------------------------------------------------------
 // standard scoring kernel (K6/K8) — v4
 //
-// Node record is 8 bytes {uint32 w0, uint32 w1}:
+// Node record is 8 bytes {uint32 w0, uint32 w1}, trees in LEVEL order
+// (v4_level_order_kernel below re-lays the packers' pre-order output once
+// per pack; left child = right_child - 1):
 //   w0 = feature(12 bits) | right_child(15 bits) << 12
 //   internal: w1 = integer KEY threshold (order-preserving transform of the
 //             f32 split value; bf16 keys live in the HIGH 16 bits)
@@ -495,10 +497,13 @@ __global__ void __launch_bounds__(WAVE) build_extended_forest_kernel(
 //             OWN id (self-loop), w1 = f32 bits of (depth + c(numInstances))
 //
 // Rows are staged in LDS as order-preserving integer keys (u16 for bf16
-// input, u32 for f32), so each visit is: ds_read_b64 node, ds_read LDS key,
-// one unsigned compare, one select — no float convert, no leaf branch, no
-// depth counter. Leaves self-loop (sentinel key 0xFF..F compares false
-// against every threshold), so the walk is a FIXED height_limit-trip loop
+// input, u32 for f32), feature-major, so each visit is: ds_read_b64 node,
+// ds_read LDS key, one unsigned compare, one subtract-with-borrow
+// (cur = right_child - (x < t)) — no float convert, no leaf branch, no
+// depth counter. Both reads are laid out against LDS bank conflicts
+// (profiles/score_layout.md). Leaves self-loop (sentinel key 0xFF..F
+// compares false against every threshold), so the walk is a FIXED
+// height_limit-trip loop
 // with zero per-chain bookkeeping; the leaf value (depth folded in, as the
 // reference's ONNX converter does: isolation_forest_converter.py:343-373)
 // is read once after the loop. Each thread walks RPT rows x 4 trees = 4*RPT
@@ -586,16 +591,99 @@ __device__ __host__ __forceinline__ int row_stride(int d) {
 }
 
 
+// ---------------------------------------------------------------------------
+// v4 records, pre-order -> level order. The packers emit pre-order trees
+// (left child at cur+1, link = right child). The walk reads them breadth-
+// first: each level contiguous and left to right, the two children of a node
+// adjacent, link = the RIGHT child's new index (left = link-1); leaves keep
+// link = own new index. At walk iteration `it` every chain sits at depth
+// `it` or rests at a shallower leaf, so the <= 32 nodes of levels 0..5 fall
+// on distinct 8-byte bank pairs of a ds_read_b64 instead of being scattered
+// over the whole pre-order array. One wave per tree; a level's nodes are
+// numbered by a ballot prefix count. Records past ncount (dead tail) and
+// single-leaf padding trees come out unchanged.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(WAVE) v4_level_order_kernel(
+    const int2* __restrict__ in,       // [Tpad][max_nodes] pre-order
+    const int32_t* __restrict__ ncnt,  // [Tpad]
+    int2* __restrict__ out,            // [Tpad][max_nodes] level order
+    int32_t max_nodes) {
+  uint16_t* order = (uint16_t*)smem;  // [max_nodes] new index -> old index
+  const int lane = threadIdx.x;
+  const int2* src = in + (int64_t)blockIdx.x * max_nodes;
+  int2* dst = out + (int64_t)blockIdx.x * max_nodes;
+  const int n = min(max(ncnt[blockIdx.x], 1), max_nodes);
+  for (int i = n + lane; i < max_nodes; i += WAVE) dst[i] = src[i];
+  if (lane == 0) order[0] = 0;
+  __syncthreads();
+  int begin = 0, end = 1;  // the current level, in new indices
+  while (begin < end) {
+    int tail = end;  // next free new index (wave-uniform)
+    for (int base = begin; base < end; base += WAVE) {
+      const int i = base + lane;
+      int2 rec = make_int2(0, 0);
+      int old = 0, right = 0;
+      bool internal = false;
+      if (i < end) {
+        old = min((int)order[i], n - 1);
+        rec = src[old];
+        right = pn_right(rec.x);
+        // a leaf links to itself; children outside the tree (a malformed
+        // record) are not followed, so every index stays below n
+        internal = right != old && right < n && old + 1 < n;
+      }
+      const uint64_t m = __ballot(internal);
+      int link = i;
+      if (internal) {
+        const int l = tail + 2 * __popcll(m & LANE_MASK_LT(lane));
+        if (l + 1 < n) {
+          order[l] = (uint16_t)(old + 1);
+          order[l + 1] = (uint16_t)right;
+          link = l + 1;
+        }
+      }
+      if (i < end)
+        dst[i] = make_int2((rec.x & ~(0x7FFF << 12)) | (link << 12), rec.y);
+      tail = min(tail + 2 * __popcll(m), n);
+    }
+    __syncthreads();  // the next level's order[] entries are written
+    begin = end;
+    end = tail;
+  }
+  // nodes no link reaches (never in a packed tree): self-loops, so that
+  // every record of the output is defined and in bounds
+  for (int i = end + lane; i < n; i += WAVE)
+    dst[i] = make_int2((src[i].x & ~(0x7FFF << 12)) | (i << 12), src[i].y);
+}
+
+// element offset of block row j inside one slab of the v4 key tile. 32-bit
+// keys: element j. 16-bit keys: P = RPT*128 words per slab, row j in word
+// (j mod P), half (j / P) — RPT=2 pairs rows tid and tid+256 in one word,
+// RPT=1 pairs rows tid and tid+128.
+template <typename KT, int RPT>
+__device__ __forceinline__ int v4_tile_slot(int j) {
+  if (sizeof(KT) == 4) return j;
+  constexpr int P = RPT * 128;
+  return (j % P) * 2 + j / P;
+}
+
 template <typename KT, int RPT, bool ROWS_LDS, int V4_ILP, bool NODES_LDS>
 __global__ void __launch_bounds__(256) score_forest_v4(
     const KT* __restrict__ X,          // raw bf16/fp16/f32 bits [N][d]
     const int2* __restrict__ nodes,    // [Tpad][max_nodes] packed v4
     const int32_t* __restrict__ ncnt,  // [Tpad]
     float* __restrict__ out,           // [N] (path sum or score)
-    int64_t N, int32_t d, int32_t dpad, int32_t Tpad, int32_t max_nodes,
+    int64_t N, int32_t d, int32_t Tpad, int32_t max_nodes,
     int32_t height_limit, float fT, float c_norm, int32_t finalize) {
   const int tid = threadIdx.x;
   const int rows_per_iter = RPT * 256;
+  // key tile, feature-major: slab f = keys of feature f for every row of the
+  // block, slab d = the all-ones leaf sentinel. FS is the slab stride in
+  // elements; row j sits at element v4_tile_slot(j) of each slab, so the 64
+  // lanes of a wave read lane-adjacent words and the bank is (lane mod 32)
+  // for ANY per-lane mix of features (the row-major tile was conflict-free
+  // only when every lane wanted the same feature).
+  constexpr int FS = RPT * 256;
 
   int2* tlds = (int2*)smem;  // [V4_ILP * max_nodes] when NODES_LDS
   KT* rows = (KT*)(tlds + (NODES_LDS ? V4_ILP * max_nodes : 0));
@@ -606,19 +694,42 @@ __global__ void __launch_bounds__(256) score_forest_v4(
 
     if (ROWS_LDS) {
       __syncthreads();  // previous iteration's readers done
-      const int64_t total = (int64_t)rows_here * d;
-      for (int64_t g = tid; g < total; g += 256) {
-        const int r = (int)(g / (uint32_t)d), c = (int)(g % (uint32_t)d);
-        rows[r * dpad + c] = key_of_bits<KT>(X[(block_row0 + r) * d + c]);
+      // each thread stages its own rows: lanes with consecutive rows store
+      // consecutive words of a slab (conflict-free), rows are fetched in
+      // 16-byte pieces when their starts are 16-byte aligned
+      constexpr int EPV = 16 / (int)sizeof(KT);
+      const bool vec = d % EPV == 0 && ((uintptr_t)X & 15) == 0;
+#pragma unroll
+      for (int r = 0; r < RPT; ++r) {
+        const int j = tid + r * 256;
+        KT* dst = rows + v4_tile_slot<KT, RPT>(j);
+        if (j < rows_here) {
+          const KT* src = X + (block_row0 + j) * d;
+          if (vec) {
+            for (int c = 0; c < d; c += EPV) {
+              union { uint4 v; KT e[EPV]; } pc;
+              pc.v = *(const uint4*)(src + c);
+#pragma unroll
+              for (int k = 0; k < EPV; ++k)
+                dst[(c + k) * FS] = key_of_bits<KT>(pc.e[k]);
+            }
+          } else {
+            for (int c = 0; c < d; ++c)
+              dst[c * FS] = key_of_bits<KT>(src[c]);
+          }
+        } else {
+          // tail block: rows past N are walked but never stored
+          for (int c = 0; c < d; ++c) dst[c * FS] = key_sentinel<KT>();
+        }
+        dst[d * FS] = key_sentinel<KT>();  // leaf sentinel slab
       }
-      for (int r = tid; r < rows_per_iter; r += 256)
-        rows[r * dpad + d] = key_sentinel<KT>();  // leaf sentinel column
       __syncthreads();
     }
 
     const KT* rb[RPT];
 #pragma unroll
-    for (int r = 0; r < RPT; ++r) rb[r] = rows + (tid + r * 256) * dpad;
+    for (int r = 0; r < RPT; ++r)
+      rb[r] = rows + v4_tile_slot<KT, RPT>(tid + r * 256);
 
     float psum[RPT];
 #pragma unroll
@@ -647,8 +758,8 @@ __global__ void __launch_bounds__(256) score_forest_v4(
 #pragma unroll
         for (int s = 0; s < V4_ILP; ++s) cur[r][s] = 0;
 
-#pragma unroll 2
-      for (int it = 0; it < height_limit; ++it) {
+      // one level of all RPT*V4_ILP chains
+      auto visit = [&]() __attribute__((always_inline)) {
         // three explicit phases so the compiler BATCHES the LDS reads
         // (8 node reads -> one wait -> 8 key reads -> one wait -> VALU)
         // instead of serializing 8 dependent read+wait round-trips.
@@ -664,9 +775,13 @@ __global__ void __launch_bounds__(256) score_forest_v4(
         for (int r = 0; r < RPT; ++r) {
 #pragma unroll
           for (int s = 0; s < V4_ILP; ++s) {
-            const int f = pn_feat(nd[r][s].x);
+            int f = pn_feat(nd[r][s].x);
             if (ROWS_LDS) {
-              kraw[r][s] = rb[r][f];
+              // keep the mask and the slab shift apart: folded into
+              // (meta << k) & mask the address costs shift+and+add, left
+              // alone it is v_and + one v_lshl_add as for the old tile
+              asm("" : "+v"(f));
+              kraw[r][s] = rb[r][f * FS];
             } else {
               // global fallback: the sentinel column does not exist in X,
               // so guard the leaf feature index.
@@ -687,11 +802,23 @@ __global__ void __launch_bounds__(256) score_forest_v4(
               x = (f < d) ? widen_key(key_of_bits<KT>(kraw[r][s]))
                           : 0xFFFFFFFFu;
             }
-            cur[r][s] = (x < (uint32_t)nd[r][s].y) ? cur[r][s] + 1
-                                                   : pn_right(nd[r][s].x);
+            // level order: link = right child, left child = link - 1; a
+            // leaf compares false (sentinel key) and keeps link = itself
+            cur[r][s] = pn_right(nd[r][s].x) - (x < (uint32_t)nd[r][s].y);
+            // keep the index whole (v_bfe, v_subbrev, next v_lshl_add):
+            // folded into the next node address it costs two more VALU
+            asm("" : "+v"(cur[r][s]));
           }
         }
+      };
+      // two levels per trip, by hand: the asm statement above counts as
+      // convergent, which rules out `#pragma unroll 2` with a remainder
+      int it = 0;
+      for (; it + 2 <= height_limit; it += 2) {
+        visit();
+        visit();
       }
+      if (it < height_limit) visit();
       // every chain rests at its leaf (self-loop); read value = depth + c(m)
 #pragma unroll
       for (int r = 0; r < RPT; ++r)
@@ -1828,10 +1955,18 @@ void launch_build_extended_forest(const float* bags, const int32_t* feat_sub,
                      n, d, k, nnz, max_nodes, height_limit);
 }
 
+void launch_v4_level_order(const void* nodes, const int32_t* ncount,
+                           void* out, int32_t Tpad, int32_t max_nodes,
+                           hipStream_t stream) {
+  hipLaunchKernelGGL(v4_level_order_kernel, dim3(Tpad), dim3(WAVE),
+                     (size_t)max_nodes * 2, stream, (const int2*)nodes, ncount,
+                     (int2*)out, max_nodes);
+}
+
 void launch_score_forest(RowDtype dt, int rpt, bool rows_lds, bool nodes_lds,
                          int ilp, const void* X, const void* nodes,
                          const int32_t* ncount, float* out, int64_t N,
-                         int32_t d, int32_t dpad, int32_t Tpad,
+                         int32_t d, int32_t Tpad,
                          int32_t max_nodes, int32_t height_limit, float fT,
                          float c_norm, int finalize, size_t lds, int blocks,
                          hipStream_t stream) {
@@ -1841,13 +1976,13 @@ void launch_score_forest(RowDtype dt, int rpt, bool rows_lds, bool nodes_lds,
       raise_lds((const void*)score_forest_v4<KT, RPT, RL, TI, true>, lds);    \
       hipLaunchKernelGGL((score_forest_v4<KT, RPT, RL, TI, true>),            \
                          dim3(blocks), dim3(256), lds, stream, (const KT*)X,  \
-                         (const int2*)nodes, ncount, out, N, d, dpad, Tpad,   \
+                         (const int2*)nodes, ncount, out, N, d, Tpad,         \
                          max_nodes, height_limit, fT, c_norm, finalize);      \
     } else {                                                                  \
       raise_lds((const void*)score_forest_v4<KT, RPT, RL, TI, false>, lds);   \
       hipLaunchKernelGGL((score_forest_v4<KT, RPT, RL, TI, false>),           \
                          dim3(blocks), dim3(256), lds, stream, (const KT*)X,  \
-                         (const int2*)nodes, ncount, out, N, d, dpad, Tpad,   \
+                         (const int2*)nodes, ncount, out, N, d, Tpad,         \
                          max_nodes, height_limit, fT, c_norm, finalize);      \
     }                                                                         \
   } while (0)

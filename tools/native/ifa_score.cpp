@@ -45,10 +45,13 @@
 #include "row_dtype.h"
 
 namespace ifa {
+void launch_v4_level_order(const void* nodes, const int32_t* ncount,
+                           void* out, int32_t Tpad, int32_t max_nodes,
+                           hipStream_t stream);
 void launch_score_forest(RowDtype dt, int rpt, bool rows_lds, bool nodes_lds,
                          int ilp, const void* X, const void* nodes,
                          const int32_t* ncount, float* out, int64_t N,
-                         int32_t d, int32_t dpad, int32_t Tpad,
+                         int32_t d, int32_t Tpad,
                          int32_t max_nodes, int32_t height_limit, float fT,
                          float c_norm, int finalize, size_t lds, int blocks,
                          hipStream_t stream);
@@ -653,9 +656,20 @@ int main(int argc, char** argv) {
                         hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(dNcount, p.ncount.data(), p.ncount.size() * 4,
                         hipMemcpyHostToDevice));
+    // pack_v4 emits pre-order records; the walk reads them in level order
+    // (as ops/gpu_engine._v4_walk_order does after its pack)
+    void* dWalk;
+    HIP_CHECK(hipMalloc(&dWalk, p.nodes.size() * 4));
+    ifa::launch_v4_level_order(dNodes, (const int32_t*)dNcount, dWalk, p.Tpad,
+                               p.mn, 0);
+    HIP_CHECK(hipGetLastError());
+    dNodes = dWalk;
     size_t node_bytes = (size_t)4 * p.mn * 8;
     bool nodes_lds = true;
-    if (node_bytes + (size_t)256 * dpad * elem > 150 * 1024) {
+    // v4 key tile: d feature slabs + the sentinel slab (feature-major,
+    // unpadded), as in ops/hip/bindings.cpp
+    const size_t slabs = (size_t)d + 1;
+    if (node_bytes + (size_t)256 * slabs * elem > 150 * 1024) {
       nodes_lds = false;
       node_bytes = 0;
     }
@@ -663,7 +677,7 @@ int main(int argc, char** argv) {
     bool rows_lds = true;
     size_t lds;
     for (;;) {
-      size_t row_bytes = (size_t)rpt * 256 * dpad * elem;
+      size_t row_bytes = (size_t)rpt * 256 * slabs * elem;
       lds = node_bytes + row_bytes;
       if (lds * 3 <= kMaxLds || (rpt == 1 && lds <= 150 * 1024)) break;
       if (rpt == 2) { rpt = 1; continue; }
@@ -676,7 +690,7 @@ int main(int argc, char** argv) {
         (N + rows_per_block - 1) / rows_per_block, 8192);
     ifa::launch_score_forest(dt, rpt, rows_lds, nodes_lds, 4, dX, dNodes,
                              (const int32_t*)dNcount, (float*)dOut, N, d,
-                             (int32_t)dpad, p.Tpad, p.mn, p.max_depth,
+                             p.Tpad, p.mn, p.max_depth,
                              (float)p.T, c_norm, 1, lds, blocks, 0);
   } else {
     // routing mirror of ops/gpu_engine.score_extended_forest (the wide-d
