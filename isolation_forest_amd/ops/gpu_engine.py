@@ -28,6 +28,7 @@ width and dtype (score_extended_forest):
 
 from __future__ import annotations
 
+import logging
 import math
 import os
 
@@ -37,6 +38,42 @@ import torch
 from ..core.forest import ExtendedForest, Forest
 from ..utils.math import avg_path_length
 from . import load_extension
+
+
+_log = logging.getLogger(__name__)
+
+
+def _row_layout(X: torch.Tensor):
+    """Classify a 2-D row view for the kernels, which address
+    ``X[r * rs + c * cs]`` with ``(rs, cs) = X.stride()``.
+
+    ``"row"``: pitched row-major, ``cs == 1`` and ``rs >= d`` (packed is
+    ``rs == d``). ``"feature"``: feature-major, ``rs == 1`` and ``cs >= N``
+    (a ``[d, N]`` buffer seen through ``.T``, a Fortran-ordered array).
+    ``None``: anything else (both strides != 1, stride 0 from ``expand``,
+    overlapping rows), which needs a packed copy. The stride torch reports
+    for a size-1 dimension is arbitrary and ignored; a view that fits both
+    layouts is ``"row"``. Pure stride arithmetic: works on CPU tensors too.
+    Mirrors ``check_x_layout`` in ops/hip/bindings.cpp.
+    """
+    N, d = int(X.shape[0]), int(X.shape[1])
+    rs, cs = X.stride()
+    if (d <= 1 or cs == 1) and (N <= 1 or rs >= d):
+        return "row"
+    if (N <= 1 or rs == 1) and (d <= 1 or cs >= N):
+        return "feature"
+    return None
+
+
+def _rows_in_place(X: torch.Tensor) -> torch.Tensor:
+    """X itself when the kernels can read it where it lies (no copy of the
+    matrix is made), else one packed row-major copy."""
+    if _row_layout(X) is not None:
+        return X
+    _log.debug("rows with strides %s (shape %s) are not consumable in place: "
+               "making one contiguous copy", tuple(X.stride()),
+               tuple(X.shape))
+    return X.contiguous()
 
 
 def _leaf_lut(n: int, device) -> torch.Tensor:
@@ -62,7 +99,7 @@ def build_forest(X: torch.Tensor, bag_idx: np.ndarray, feat_sub: np.ndarray,
     max_nodes = 2 * n - 1
     bag_t = torch.from_numpy(np.ascontiguousarray(bag_idx)).to(device)
     fs_t = torch.from_numpy(np.ascontiguousarray(feat_sub, dtype=np.int32)).to(device)
-    bags = ext.bag_gather(X.contiguous(), bag_t)
+    bags = ext.bag_gather(_rows_in_place(X), bag_t)
     feat, value, right, count, ncount, depth = ext.build_forest(
         bags, fs_t, seed, tree_id_offset, _leaf_lut(n, device), max_nodes,
         height_limit,
@@ -109,7 +146,7 @@ def build_extended_forest(X: torch.Tensor, bag_idx: np.ndarray,
     nnz = min(rp.extension_level + 1, rp.num_features)
     bag_t = torch.from_numpy(np.ascontiguousarray(bag_idx)).to(device)
     fs_t = torch.from_numpy(np.ascontiguousarray(feat_sub, dtype=np.int32)).to(device)
-    bags = ext.bag_gather(X.contiguous(), bag_t)
+    bags = ext.bag_gather(_rows_in_place(X), bag_t)
     (feat, value, right, count, ncount, hidx, hw, off64,
      depth) = ext.build_extended_forest(
         bags, fs_t, seed, tree_id_offset, _leaf_lut(n, device), nnz, max_nodes,
@@ -1044,11 +1081,11 @@ def score_forest(model, X: torch.Tensor, finalize: bool = True) -> torch.Tensor:
         aos, ncount, extra = _device_forest(
             model, X.device, v4_key=("wide", kind))
         return ext.score_forest_wide(
-            X.contiguous(), aos, extra["height"], c, finalize,
+            _rows_in_place(X), aos, extra["height"], c, finalize,
         )
     aos, ncount, extra = _device_forest(model, X.device, v4_key=(d, kind))
     return ext.score_forest(
-        X.contiguous(), aos, ncount, forest.num_trees, extra["height"], c,
+        _rows_in_place(X), aos, ncount, forest.num_trees, extra["height"], c,
         finalize,
     )
 
@@ -1079,7 +1116,7 @@ def score_extended_forest(model, X: torch.Tensor, finalize: bool = True) -> torc
         aos, ncount, extra = _device_forest(model, X.device,
                                             v4_key="eif_wide")
         return ext.score_extended_wide(
-            X.contiguous(), aos, extra["hidx"], extra["hw"], c, finalize,
+            _rows_in_place(X), aos, extra["hidx"], extra["hw"], c, finalize,
         )
     # routing (measured crossovers, profiles/r01_bench_and_kernels.md):
     # nnz <= 5 with uniform hyperplane widths -> fixed-trip sparse v2;
@@ -1097,7 +1134,7 @@ def score_extended_forest(model, X: torch.Tensor, finalize: bool = True) -> torc
         aos, ncount, extra = _device_forest(
             model, X.device, v4_key=("eif0", d, _row_kind(X.dtype)))
         return ext.score_forest(
-            X.contiguous(), aos, ncount, forest.num_trees, extra["height"],
+            _rows_in_place(X), aos, ncount, forest.num_trees, extra["height"],
             c, finalize,
         )
     if nnz <= 5 and _eif_uniform_nnz(forest):
@@ -1115,7 +1152,7 @@ def score_extended_forest(model, X: torch.Tensor, finalize: bool = True) -> torc
             aos, ncount, extra = _device_forest(
                 model, X.device, v4_key="eif_sparse")
             return ext.score_extended_sparse_v2(
-                X.contiguous(), aos, extra["values"], extra["hidx"],
+                _rows_in_place(X), aos, extra["values"], extra["hidx"],
                 extra["hw"], ncount, extra["height"], c, finalize,
             )
     # densified hyperplanes (nnz < d) carry weight 0 on unselected
@@ -1145,7 +1182,7 @@ def score_extended_forest(model, X: torch.Tensor, finalize: bool = True) -> torc
                 aos, ncount, extra = _device_forest(
                     model, X.device, v4_key=("eif_dense3", D))
                 return ext.score_extended_dense_v3(
-                    X.contiguous(), aos, extra["values"], extra["hwp"],
+                    _rows_in_place(X), aos, extra["values"], extra["hwp"],
                     ncount, extra["height"], c, finalize,
                 )
         if d <= 64:  # v2's f32 staging exceeds LDS past D=64
@@ -1154,14 +1191,14 @@ def score_extended_forest(model, X: torch.Tensor, finalize: bool = True) -> torc
                 aos, ncount, extra = _device_forest(
                     model, X.device, v4_key=("eif_dense", D))
                 return ext.score_extended_dense_v2(
-                    X.contiguous(), aos, extra["values"], extra["hw"],
+                    _rows_in_place(X), aos, extra["values"], extra["hw"],
                     ncount, extra["height"], c, finalize,
                 )
         # deep forests overflow the dense kernel's LDS weight staging:
         # fall through to the general kernel (nodes from global if needed)
     aos, ncount, extra = _device_forest(model, X.device)
     return ext.score_extended_forest(
-        X.contiguous(), aos, extra["hidx"], extra["hw"], ncount, c, finalize
+        _rows_in_place(X), aos, extra["hidx"], extra["hw"], ncount, c, finalize
     )
 
 
@@ -1173,9 +1210,7 @@ def score_extended_forest(model, X: torch.Tensor, finalize: bool = True) -> torc
 def _explain_on_cpu(fn, forest, X: torch.Tensor, finalize: bool, why: str):
     """Forests past the packed-record caps: CPU oracle, result moved to X's
     device (a correctness path; there are no wide-record explain kernels)."""
-    import logging
-
-    logging.getLogger(__name__).warning(
+    _log.warning(
         "feature_contributions: %s; computing on the CPU oracle", why)
     Xc = X.detach().float().cpu().contiguous().numpy()
     return torch.from_numpy(fn(forest, Xc, finalize)).to(X.device)
@@ -1207,7 +1242,7 @@ def explain_forest(model, X: torch.Tensor, finalize: bool = True) -> torch.Tenso
     ext = load_extension()
     aos, ncount, extra = _device_forest(
         model, X.device, v4_key=("explain", d, _row_kind(X.dtype)))
-    return ext.explain_forest(X.contiguous(), aos, ncount, extra["height"],
+    return ext.explain_forest(_rows_in_place(X), aos, ncount, extra["height"],
                               finalize)
 
 
@@ -1235,5 +1270,5 @@ def explain_extended_forest(model, X: torch.Tensor,
     ext = load_extension()
     aos, ncount, extra = _device_forest(model, X.device, v4_key="eif_explain")
     return ext.explain_extended_forest(
-        X.contiguous(), aos, extra["hidx"], extra["hw"], extra["dl"],
+        _rows_in_place(X), aos, extra["hidx"], extra["hw"], extra["dl"],
         extra["dr"], finalize)

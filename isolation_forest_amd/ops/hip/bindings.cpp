@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "row_dtype.h"
@@ -14,6 +15,7 @@ namespace ifa {
 
 void launch_bag_gather(RowDtype dt, const void* X, const int64_t* bag_idx,
                        float* bags, int64_t T, int64_t n, int64_t d,
+                       int64_t rs, int64_t cs,
                        hipStream_t stream);
 
 void launch_build_forest(const float* bags, const int32_t* feat_sub,
@@ -42,7 +44,7 @@ void launch_v4_level_order(const void* nodes, const int32_t* ncount,
 void launch_score_forest(RowDtype dt, int rpt, bool rows_lds, bool nodes_lds,
                          int ilp, const void* X, const void* nodes,
                          const int32_t* ncount, float* out, int64_t N,
-                         int32_t d, int32_t Tpad,
+                         int32_t d, int64_t rs, int64_t cs, int32_t Tpad,
                          int32_t max_nodes, int32_t height_limit, float fT,
                          float c_norm, int finalize, size_t lds, int blocks,
                          hipStream_t stream);
@@ -50,16 +52,18 @@ void launch_score_forest(RowDtype dt, int rpt, bool rows_lds, bool nodes_lds,
 void launch_score_extended_dense(RowDtype dt, bool rows_lds, bool wlds,
                                  const void* X, const void* nodes,
                                  const float* hw, const int32_t* ncount,
-                                 float* out, int64_t N, int32_t d,
-                                 int32_t dpad, int32_t T, int32_t max_nodes,
-                                 float fT, float c_norm, int finalize,
-                                 size_t lds, int blocks, hipStream_t stream);
+                                 float* out, int64_t N, int32_t d, int64_t rs,
+                                 int64_t cs, int32_t dpad, int32_t T,
+                                 int32_t max_nodes, float fT, float c_norm,
+                                 int finalize, size_t lds, int blocks,
+                                 hipStream_t stream);
 
 void launch_score_extended_forest(RowDtype dt, bool rows_lds, bool hyper_lds,
                                   bool nodes_lds, const void* X,
                                   const void* nodes, const int32_t* hidx,
                                   const float* hw, const int32_t* ncount,
-                                  float* out, int64_t N, int32_t d, int32_t T,
+                                  float* out, int64_t N, int32_t d, int64_t rs,
+                                  int64_t cs, int32_t T,
                                   int32_t max_nodes, int32_t nnz, float fT,
                                   float c_norm, int finalize, size_t lds,
                                   int blocks, hipStream_t stream);
@@ -68,7 +72,8 @@ void launch_score_extended_sparse_v2(RowDtype dt, int nnz, const void* X,
                                      const void* nodes, const float* values,
                                      const int32_t* hidx, const float* hw,
                                      const int32_t* ncount, float* out,
-                                     int64_t N, int32_t d, int32_t dpad,
+                                     int64_t N, int32_t d, int64_t rs,
+                                     int64_t cs, int32_t dpad,
                                      int32_t T, int32_t max_nodes,
                                      int32_t height_limit, float fT,
                                      float c_norm, int finalize, size_t lds,
@@ -78,6 +83,7 @@ void launch_score_extended_dense_v2(RowDtype dt, int D, const void* X,
                                     const void* nodes, const float* values,
                                     const float* hw, const int32_t* ncount,
                                     float* out, int64_t N, int32_t d,
+                                    int64_t rs, int64_t cs,
                                     int32_t T, int32_t max_nodes,
                                     int32_t height_limit, float fT,
                                     float c_norm, int finalize, size_t lds,
@@ -87,7 +93,8 @@ void launch_score_extended_dense_v3(int D, bool rpt2, const void* X,
                                     const void* nodes, const float* values,
                                     const uint32_t* hwp,
                                     const int32_t* ncount, float* out,
-                                    int64_t N, int32_t d, int32_t T,
+                                    int64_t N, int32_t d, int64_t rs,
+                                    int64_t cs, int32_t T,
                                     int32_t max_nodes, int32_t height_limit,
                                     float fT, float c_norm, int finalize,
                                     size_t lds, int blocks,
@@ -96,17 +103,20 @@ void launch_score_extended_dense_v3(int D, bool rpt2, const void* X,
 void launch_score_extended_dense_nonfinite_rows(
     RowDtype dt, bool packed_w, const void* X, const void* nodes,
     const float* values, const void* wts, float* out, int64_t N, int32_t d,
+    int64_t rs, int64_t cs,
     int32_t D, int32_t T, int32_t max_nodes, int32_t height_limit, float fT,
     float c_norm, int finalize, int blocks, hipStream_t stream);
 void launch_score_forest_wide(RowDtype dt, const void* X, const void* nodes,
-                              float* out, int64_t N, int32_t d, int32_t T,
+                              float* out, int64_t N, int32_t d, int64_t rs,
+                              int64_t cs, int32_t T,
                               int64_t max_nodes, int32_t height_limit,
                               float fT, float c_norm, int finalize,
                               int blocks, hipStream_t stream);
 
 void launch_score_extended_wide(RowDtype dt, const void* X, const void* nodes,
                                 const int32_t* hidx, const float* hw,
-                                float* out, int64_t N, int32_t d, int32_t T,
+                                float* out, int64_t N, int32_t d, int64_t rs,
+                                int64_t cs, int32_t T,
                                 int64_t max_nodes, int32_t nnz, float fT,
                                 float c_norm, int finalize, int blocks,
                                 hipStream_t stream);
@@ -114,17 +124,19 @@ void launch_score_extended_wide(RowDtype dt, const void* X, const void* nodes,
 void launch_explain_forest(RowDtype dt, int mode, int rpt, bool nodes_lds,
                            const void* X, const void* nodes,
                            const int32_t* ncount, float* out, int64_t N,
-                           int32_t d, int32_t dpad, int32_t astride,
-                           int32_t T, int32_t max_nodes, int32_t tps,
-                           int32_t height_limit, float fT, int finalize,
-                           size_t lds, int blocks, hipStream_t stream);
+                           int32_t d, int64_t rs, int64_t cs, int32_t dpad,
+                           int32_t astride, int32_t T, int32_t max_nodes,
+                           int32_t tps, int32_t height_limit, float fT,
+                           int finalize, size_t lds, int blocks,
+                           hipStream_t stream);
 
 void launch_explain_extended(RowDtype dt, const void* X, const void* nodes,
                              const int32_t* hidx, const float* hw,
                              const float* dl, const float* dr, float* out,
-                             int64_t N, int32_t d, int32_t T,
-                             int32_t max_nodes, int32_t nnz, float fT,
-                             int finalize, int blocks, hipStream_t stream);
+                             int64_t N, int32_t d, int64_t rs, int64_t cs,
+                             int32_t T, int32_t max_nodes, int32_t nnz,
+                             float fT, int finalize, int blocks,
+                             hipStream_t stream);
 
 }  // namespace ifa
 
@@ -160,21 +172,47 @@ void check_x(const torch::Tensor& X) {
               "X must be float32, bfloat16 or float16");
 }
 
+// element strides the kernels address X with: X[r][c] = X[r * rs + c * cs]
+struct XLayout {
+  int64_t rs, cs;
+};
+
+// Layout contract for a checked X (docs/API.md "Input layouts"): consumed in
+// place when pitched row-major (stride(1) == 1, stride(0) >= d) or
+// feature-major (stride(0) == 1, stride(1) >= N), at any storage offset and
+// alignment. The stride torch reports for a size-1 dimension is arbitrary
+// and ignored (that index is always 0); it is returned normalised so the
+// kernels' alignment tests see the packed value. A view that fits both
+// layouts is row-major. Everything else is the caller's to copy
+// (gpu_engine._rows_in_place).
+XLayout check_x_layout(const torch::Tensor& X) {
+  const int64_t N = X.size(0), d = X.size(1);
+  const int64_t s0 = X.stride(0), s1 = X.stride(1);
+  const bool row = (d <= 1 || s1 == 1) && (N <= 1 || s0 >= d);
+  const bool feat = (N <= 1 || s0 == 1) && (d <= 1 || s1 >= N);
+  TORCH_CHECK(row || feat,
+              "X must be pitched row-major (stride(1) == 1, stride(0) >= d) "
+              "or feature-major (stride(0) == 1, stride(1) >= N); got shape [",
+              N, ", ", d, "] with strides (", s0, ", ", s1, ")");
+  if (row) return {N <= 1 ? std::max<int64_t>(d, 1) : s0, 1};
+  return {1, s1};
+}
+
 }  // namespace
 
 torch::Tensor bag_gather(torch::Tensor X, torch::Tensor bag_idx) {
   CHECK_CUDA(X);
-  CHECK_CONTIG(X);
   CHECK_CUDA(bag_idx);
   CHECK_CONTIG(bag_idx);
   check_x(X);
+  const XLayout xl = check_x_layout(X);
   TORCH_CHECK(bag_idx.dim() == 2 && bag_idx.scalar_type() == torch::kInt64,
               "bag_idx must be int64 [T, n]");
   int64_t T = bag_idx.size(0), n = bag_idx.size(1), d = X.size(1);
   auto bags = torch::empty({T, n, d}, X.options().dtype(torch::kFloat32));
   ifa::launch_bag_gather(row_dtype(X), X.data_ptr(),
                          bag_idx.data_ptr<int64_t>(), bags.data_ptr<float>(),
-                         T, n, d, current_stream());
+                         T, n, d, xl.rs, xl.cs, current_stream());
   return bags;
 }
 
@@ -292,11 +330,11 @@ torch::Tensor score_forest(torch::Tensor X, torch::Tensor nodes_packed,
                            int64_t height_limit, double c_norm,
                            bool finalize) {
   CHECK_CUDA(X);
-  CHECK_CONTIG(X);
   CHECK_CUDA(nodes_packed);
   CHECK_CONTIG(nodes_packed);
   CHECK_CUDA(ncount);
   check_x(X);
+  const XLayout xl = check_x_layout(X);
   TORCH_CHECK(nodes_packed.dim() == 3 && nodes_packed.size(2) == 2 &&
                   nodes_packed.scalar_type() == torch::kInt32,
               "nodes must be packed int32 [Tpad, max_nodes, 2]");
@@ -370,7 +408,7 @@ torch::Tensor score_forest(torch::Tensor X, torch::Tensor nodes_packed,
   ifa::launch_score_forest(dt, rpt, rows_lds, nodes_lds, ilp, X.data_ptr(),
                            nodes_packed.data_ptr<int32_t>(),
                            ncount.data_ptr<int32_t>(), out.data_ptr<float>(),
-                           N, (int32_t)d, (int32_t)Tpad,
+                           N, (int32_t)d, xl.rs, xl.cs, (int32_t)Tpad,
                            (int32_t)max_nodes, (int32_t)height_limit,
                            (float)num_trees, (float)c_norm, finalize ? 1 : 0,
                            lds, blocks, current_stream());
@@ -384,7 +422,6 @@ torch::Tensor score_extended_forest(torch::Tensor X,
                                     torch::Tensor ncount, double c_norm,
                                     bool finalize) {
   CHECK_CUDA(X);
-  CHECK_CONTIG(X);
   CHECK_CUDA(nodes_packed);
   CHECK_CONTIG(nodes_packed);
   CHECK_CUDA(hidx);
@@ -392,6 +429,7 @@ torch::Tensor score_extended_forest(torch::Tensor X,
   CHECK_CUDA(hw);
   CHECK_CONTIG(hw);
   check_x(X);
+  const XLayout xl = check_x_layout(X);
   TORCH_CHECK(nodes_packed.dim() == 3 && nodes_packed.size(2) == 2 &&
                   nodes_packed.scalar_type() == torch::kInt32,
               "nodes must be packed int32 [T, max_nodes, 2]");
@@ -422,8 +460,8 @@ torch::Tensor score_extended_forest(torch::Tensor X,
     size_t lds = node_bytes + (wlds ? w_bytes : 0) + (rows_lds ? drow_bytes : 0);
     ifa::launch_score_extended_dense(
         dt, rows_lds, wlds, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
-        hw.data_ptr<float>(), ncount.data_ptr<int32_t>(),
-        out.data_ptr<float>(), N, (int32_t)d, (int32_t)dpad, (int32_t)T,
+        hw.data_ptr<float>(), ncount.data_ptr<int32_t>(), out.data_ptr<float>(),
+        N, (int32_t)d, xl.rs, xl.cs, (int32_t)dpad, (int32_t)T,
         (int32_t)max_nodes, (float)T, (float)c_norm, finalize ? 1 : 0, lds,
         blocks, current_stream());
     return out;
@@ -442,7 +480,8 @@ torch::Tensor score_extended_forest(torch::Tensor X,
       dt, rows_lds, hyper_lds, nodes_lds, X.data_ptr(),
       nodes_packed.data_ptr<int32_t>(), hidx.data_ptr<int32_t>(),
       hw.data_ptr<float>(), ncount.data_ptr<int32_t>(), out.data_ptr<float>(),
-      N, (int32_t)d, (int32_t)T, (int32_t)max_nodes, (int32_t)nnz, (float)T,
+      N, (int32_t)d, xl.rs, xl.cs, (int32_t)T, (int32_t)max_nodes,
+      (int32_t)nnz, (float)T,
       (float)c_norm, finalize ? 1 : 0, lds, blocks, current_stream());
   return out;
 }
@@ -454,7 +493,6 @@ torch::Tensor score_extended_dense_v2(torch::Tensor X,
                                       int64_t height_limit, double c_norm,
                                       bool finalize) {
   CHECK_CUDA(X);
-  CHECK_CONTIG(X);
   CHECK_CUDA(nodes_packed);
   CHECK_CONTIG(nodes_packed);
   CHECK_CUDA(values);
@@ -463,6 +501,7 @@ torch::Tensor score_extended_dense_v2(torch::Tensor X,
   CHECK_CONTIG(hw);
   CHECK_CUDA(ncount);
   check_x(X);
+  const XLayout xl = check_x_layout(X);
   TORCH_CHECK(nodes_packed.dim() == 3 && nodes_packed.size(2) == 2 &&
                   nodes_packed.scalar_type() == torch::kInt32,
               "nodes must be packed int32 [T, max_nodes, 2]");
@@ -482,14 +521,14 @@ torch::Tensor score_extended_dense_v2(torch::Tensor X,
   ifa::launch_score_extended_dense_v2(
       row_dtype(X), D, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
       values.data_ptr<float>(), hw.data_ptr<float>(),
-      ncount.data_ptr<int32_t>(), out.data_ptr<float>(), N, (int32_t)d,
-      (int32_t)T, (int32_t)max_nodes, (int32_t)height_limit, (float)T,
+      ncount.data_ptr<int32_t>(), out.data_ptr<float>(), N, (int32_t)d, xl.rs,
+      xl.cs, (int32_t)T, (int32_t)max_nodes, (int32_t)height_limit, (float)T,
       (float)c_norm, finalize ? 1 : 0, lds, blocks, current_stream());
   // rows with an inf/NaN cell: strict-order rescoring (see the kernel)
   ifa::launch_score_extended_dense_nonfinite_rows(
       row_dtype(X), false, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
       values.data_ptr<float>(), hw.data_ptr<float>(), out.data_ptr<float>(),
-      N, (int32_t)d, (int32_t)D, (int32_t)T, (int32_t)max_nodes,
+      N, (int32_t)d, xl.rs, xl.cs, (int32_t)D, (int32_t)T, (int32_t)max_nodes,
       (int32_t)height_limit, (float)T, (float)c_norm, finalize ? 1 : 0,
       (int)std::min<int64_t>((N + 255) / 256, 8192), current_stream());
   return out;
@@ -502,7 +541,6 @@ torch::Tensor score_extended_dense_v3(torch::Tensor X,
                                       int64_t height_limit, double c_norm,
                                       bool finalize) {
   CHECK_CUDA(X);
-  CHECK_CONTIG(X);
   CHECK_CUDA(nodes_packed);
   CHECK_CONTIG(nodes_packed);
   CHECK_CUDA(values);
@@ -511,6 +549,7 @@ torch::Tensor score_extended_dense_v3(torch::Tensor X,
   CHECK_CONTIG(hwp);
   CHECK_CUDA(ncount);
   check_x(X);
+  const XLayout xl = check_x_layout(X);
   TORCH_CHECK(is_bf16(X),
               "dense v3 requires bf16 rows (f32/fp16 rows route to v2)");
   TORCH_CHECK(nodes_packed.dim() == 3 && nodes_packed.size(2) == 2 &&
@@ -538,17 +577,16 @@ torch::Tensor score_extended_dense_v3(torch::Tensor X,
   ifa::launch_score_extended_dense_v3(
       D, rpt2, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
       values.data_ptr<float>(), (const uint32_t*)hwp.data_ptr<int32_t>(),
-      ncount.data_ptr<int32_t>(), out.data_ptr<float>(), N, (int32_t)d,
-      (int32_t)T, (int32_t)max_nodes, (int32_t)height_limit, (float)T,
+      ncount.data_ptr<int32_t>(), out.data_ptr<float>(), N, (int32_t)d, xl.rs,
+      xl.cs, (int32_t)T, (int32_t)max_nodes, (int32_t)height_limit, (float)T,
       (float)c_norm, finalize ? 1 : 0, lds, blocks, current_stream());
   // rows with an inf/NaN cell: strict-order rescoring (see the kernel)
   ifa::launch_score_extended_dense_nonfinite_rows(
       ifa::ROW_BF16, true, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
-      values.data_ptr<float>(), hwp.data_ptr<int32_t>(),
-      out.data_ptr<float>(), N, (int32_t)d, (int32_t)D, (int32_t)T,
-      (int32_t)max_nodes, (int32_t)height_limit, (float)T, (float)c_norm,
-      finalize ? 1 : 0, (int)std::min<int64_t>((N + 255) / 256, 8192),
-      current_stream());
+      values.data_ptr<float>(), hwp.data_ptr<int32_t>(), out.data_ptr<float>(),
+      N, (int32_t)d, xl.rs, xl.cs, (int32_t)D, (int32_t)T, (int32_t)max_nodes,
+      (int32_t)height_limit, (float)T, (float)c_norm, finalize ? 1 : 0,
+      (int)std::min<int64_t>((N + 255) / 256, 8192), current_stream());
   return out;
 }
 
@@ -560,7 +598,6 @@ torch::Tensor score_extended_sparse_v2(torch::Tensor X,
                                        int64_t height_limit, double c_norm,
                                        bool finalize) {
   CHECK_CUDA(X);
-  CHECK_CONTIG(X);
   CHECK_CUDA(nodes_packed);
   CHECK_CONTIG(nodes_packed);
   CHECK_CUDA(values);
@@ -571,6 +608,7 @@ torch::Tensor score_extended_sparse_v2(torch::Tensor X,
   CHECK_CONTIG(hw);
   CHECK_CUDA(ncount);
   check_x(X);
+  const XLayout xl = check_x_layout(X);
   int64_t N = X.size(0), d = X.size(1);
   int64_t T = nodes_packed.size(0), max_nodes = nodes_packed.size(1);
   int64_t nnz = hidx.size(2);
@@ -592,11 +630,11 @@ torch::Tensor score_extended_sparse_v2(torch::Tensor X,
   int blocks = (int)std::min<int64_t>((N + 511) / 512, 8192);
   ifa::launch_score_extended_sparse_v2(
       dt, (int)nnz, X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
-      values.data_ptr<float>(), hidx.data_ptr<int32_t>(),
-      hw.data_ptr<float>(), ncount.data_ptr<int32_t>(),
-      out.data_ptr<float>(), N, (int32_t)d, (int32_t)dpad, (int32_t)T,
-      (int32_t)max_nodes, (int32_t)height_limit, (float)T, (float)c_norm,
-      finalize ? 1 : 0, lds, blocks, current_stream());
+      values.data_ptr<float>(), hidx.data_ptr<int32_t>(), hw.data_ptr<float>(),
+      ncount.data_ptr<int32_t>(), out.data_ptr<float>(), N, (int32_t)d, xl.rs,
+      xl.cs, (int32_t)dpad, (int32_t)T, (int32_t)max_nodes,
+      (int32_t)height_limit, (float)T, (float)c_norm, finalize ? 1 : 0, lds,
+      blocks, current_stream());
   return out;
 }
 
@@ -604,10 +642,10 @@ torch::Tensor score_forest_wide(torch::Tensor X, torch::Tensor nodes_wide,
                                 int64_t height_limit, double c_norm,
                                 bool finalize) {
   CHECK_CUDA(X);
-  CHECK_CONTIG(X);
   CHECK_CUDA(nodes_wide);
   CHECK_CONTIG(nodes_wide);
   check_x(X);
+  const XLayout xl = check_x_layout(X);
   TORCH_CHECK(nodes_wide.dim() == 3 && nodes_wide.size(2) == 4 &&
                   nodes_wide.scalar_type() == torch::kInt32,
               "nodes must be wide int32 [T, max_nodes, 4]");
@@ -618,7 +656,7 @@ torch::Tensor score_forest_wide(torch::Tensor X, torch::Tensor nodes_wide,
   int blocks = (int)std::min<int64_t>((N + 255) / 256, 8192);
   ifa::launch_score_forest_wide(
       row_dtype(X), X.data_ptr(), nodes_wide.data_ptr<int32_t>(),
-      out.data_ptr<float>(), N, (int32_t)d, (int32_t)T, max_nodes,
+      out.data_ptr<float>(), N, (int32_t)d, xl.rs, xl.cs, (int32_t)T, max_nodes,
       (int32_t)height_limit, (float)T, (float)c_norm, finalize ? 1 : 0,
       blocks, current_stream());
   return out;
@@ -628,7 +666,6 @@ torch::Tensor score_extended_wide(torch::Tensor X, torch::Tensor nodes_wide,
                                   torch::Tensor hidx, torch::Tensor hw,
                                   double c_norm, bool finalize) {
   CHECK_CUDA(X);
-  CHECK_CONTIG(X);
   CHECK_CUDA(nodes_wide);
   CHECK_CONTIG(nodes_wide);
   CHECK_CUDA(hidx);
@@ -636,6 +673,7 @@ torch::Tensor score_extended_wide(torch::Tensor X, torch::Tensor nodes_wide,
   CHECK_CUDA(hw);
   CHECK_CONTIG(hw);
   check_x(X);
+  const XLayout xl = check_x_layout(X);
   TORCH_CHECK(nodes_wide.dim() == 3 && nodes_wide.size(2) == 4 &&
                   nodes_wide.scalar_type() == torch::kInt32,
               "nodes must be wide int32 [T, max_nodes, 4]");
@@ -647,8 +685,8 @@ torch::Tensor score_extended_wide(torch::Tensor X, torch::Tensor nodes_wide,
   int blocks = (int)std::min<int64_t>((N + 255) / 256, 8192);
   ifa::launch_score_extended_wide(
       row_dtype(X), X.data_ptr(), nodes_wide.data_ptr<int32_t>(),
-      hidx.data_ptr<int32_t>(), hw.data_ptr<float>(), out.data_ptr<float>(),
-      N, (int32_t)d, (int32_t)T, max_nodes, (int32_t)nnz, (float)T,
+      hidx.data_ptr<int32_t>(), hw.data_ptr<float>(), out.data_ptr<float>(), N,
+      (int32_t)d, xl.rs, xl.cs, (int32_t)T, max_nodes, (int32_t)nnz, (float)T,
       (float)c_norm, finalize ? 1 : 0, blocks, current_stream());
   return out;
 }
@@ -659,12 +697,12 @@ torch::Tensor explain_forest(torch::Tensor X, torch::Tensor nodes_explain,
                              torch::Tensor ncount, int64_t height_limit,
                              bool finalize) {
   CHECK_CUDA(X);
-  CHECK_CONTIG(X);
   CHECK_CUDA(nodes_explain);
   CHECK_CONTIG(nodes_explain);
   CHECK_CUDA(ncount);
   CHECK_CONTIG(ncount);
   check_x(X);
+  const XLayout xl = check_x_layout(X);
   TORCH_CHECK(nodes_explain.dim() == 3 && nodes_explain.size(2) == 4 &&
                   nodes_explain.scalar_type() == torch::kInt32,
               "nodes must be explain records int32 [T, max_nodes, 4]");
@@ -747,11 +785,11 @@ torch::Tensor explain_forest(torch::Tensor X, torch::Tensor nodes_explain,
   int blocks = (int)std::min<int64_t>(
       (N + rows_per_block - 1) / rows_per_block, max_blocks);
   ifa::launch_explain_forest(
-      dt, mode, rpt, nodes_lds, X.data_ptr(),
-      nodes_explain.data_ptr<int32_t>(), ncount.data_ptr<int32_t>(),
-      out.data_ptr<float>(), N, (int32_t)d, (int32_t)dpad, (int32_t)astride,
-      (int32_t)T, (int32_t)max_nodes, (int32_t)tps, (int32_t)height_limit,
-      (float)T, finalize ? 1 : 0, lds, blocks, current_stream());
+      dt, mode, rpt, nodes_lds, X.data_ptr(), nodes_explain.data_ptr<int32_t>(),
+      ncount.data_ptr<int32_t>(), out.data_ptr<float>(), N, (int32_t)d, xl.rs,
+      xl.cs, (int32_t)dpad, (int32_t)astride, (int32_t)T, (int32_t)max_nodes,
+      (int32_t)tps, (int32_t)height_limit, (float)T, finalize ? 1 : 0, lds,
+      blocks, current_stream());
   return out;
 }
 
@@ -762,7 +800,6 @@ torch::Tensor explain_extended_forest(torch::Tensor X,
                                       torch::Tensor dl, torch::Tensor dr,
                                       bool finalize) {
   CHECK_CUDA(X);
-  CHECK_CONTIG(X);
   CHECK_CUDA(nodes_packed);
   CHECK_CONTIG(nodes_packed);
   CHECK_CUDA(hidx);
@@ -774,6 +811,7 @@ torch::Tensor explain_extended_forest(torch::Tensor X,
   CHECK_CUDA(dr);
   CHECK_CONTIG(dr);
   check_x(X);
+  const XLayout xl = check_x_layout(X);
   TORCH_CHECK(nodes_packed.dim() == 3 && nodes_packed.size(2) == 2 &&
                   nodes_packed.scalar_type() == torch::kInt32,
               "nodes must be packed int32 [T, max_nodes, 2]");
@@ -805,9 +843,9 @@ torch::Tensor explain_extended_forest(torch::Tensor X,
   ifa::launch_explain_extended(
       row_dtype(X), X.data_ptr(), nodes_packed.data_ptr<int32_t>(),
       hidx.data_ptr<int32_t>(), hw.data_ptr<float>(), dl.data_ptr<float>(),
-      dr.data_ptr<float>(), out.data_ptr<float>(), N, (int32_t)d, (int32_t)T,
-      (int32_t)max_nodes, (int32_t)nnz, (float)T, finalize ? 1 : 0, blocks,
-      current_stream());
+      dr.data_ptr<float>(), out.data_ptr<float>(), N, (int32_t)d, xl.rs, xl.cs,
+      (int32_t)T, (int32_t)max_nodes, (int32_t)nnz, (float)T, finalize ? 1 : 0,
+      blocks, current_stream());
   return out;
 }
 

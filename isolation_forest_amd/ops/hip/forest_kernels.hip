@@ -92,6 +92,11 @@ struct SegEntry {
 
 // ---------------------------------------------------------------------------
 // bag gather: bags[T][n][d] (f32) <- X[N][d] (f32, bf16 or fp16) at idx[T][n]
+//
+// Every kernel that reads X takes its two element strides: X[r][c] sits at
+// X[r * rs + c * cs] (64-bit offsets). The bindings admit pitched row-major
+// (cs == 1, rs >= d) and feature-major (rs == 1, cs >= N) sources; outputs
+// and LDS tiles do not depend on the source layout.
 // ---------------------------------------------------------------------------
 
 // 16-bit rows come in two formats. uint16_t as the element/key type means
@@ -130,14 +135,14 @@ template <typename XT>
 __global__ void bag_gather_kernel(const XT* __restrict__ X,
                                   const int64_t* __restrict__ bag_idx,
                                   float* __restrict__ bags, int64_t T, int64_t n,
-                                  int64_t d) {
+                                  int64_t d, int64_t rs, int64_t cs) {
   int64_t total = T * n * d;
   for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total;
        g += (int64_t)gridDim.x * blockDim.x) {
     int64_t j = g % d;
     int64_t ts = g / d;  // t*n + s
     int64_t row = bag_idx[ts];
-    bags[g] = load_feat<XT>(X, row * d + j);
+    bags[g] = load_feat<XT>(X, row * rs + j * cs);
   }
 }
 
@@ -667,16 +672,28 @@ __device__ __forceinline__ int v4_tile_slot(int j) {
   return (j % P) * 2 + j / P;
 }
 
-template <typename KT, int RPT, bool ROWS_LDS, int V4_ILP, bool NODES_LDS>
-__global__ void __launch_bounds__(256) score_forest_v4(
+// PACKED: the source is packed [N][d] and the strides fold to (d, 1) at
+// compile time (entry point score_forest_v4_packed, below). Runtime strides
+// cost the packed 20M x 32 pass 0.3-0.5 % (profiles/strided.md). The packed
+// entry point exists only for rows and nodes staged in LDS at ILP 4, the
+// shape that pass runs; everything else has one entry point for all layouts.
+// More would push tools/native/ifa_score, which links every kernel, past the
+// 2048 KB that tools/lint_offline.py allows any file of the tree
+// (tests/test_timing_and_bench.py runs it after the build).
+template <typename KT, int RPT, bool ROWS_LDS, int V4_ILP, bool NODES_LDS,
+          bool PACKED>
+__device__ __forceinline__ void score_forest_v4_body(
     const KT* __restrict__ X,          // raw bf16/fp16/f32 bits [N][d]
     const int2* __restrict__ nodes,    // [Tpad][max_nodes] packed v4
     const int32_t* __restrict__ ncnt,  // [Tpad]
     float* __restrict__ out,           // [N] (path sum or score)
     int64_t N, int32_t d, int32_t Tpad, int32_t max_nodes,
-    int32_t height_limit, float fT, float c_norm, int32_t finalize) {
+    int32_t height_limit, float fT, float c_norm, int32_t finalize,
+    int64_t rs_, int64_t cs_) {
   const int tid = threadIdx.x;
   const int rows_per_iter = RPT * 256;
+  const int64_t rs = PACKED ? (int64_t)d : rs_;
+  const int64_t cs = PACKED ? (int64_t)1 : cs_;
   // key tile, feature-major: slab f = keys of feature f for every row of the
   // block, slab d = the all-ones leaf sentinel. FS is the slab stride in
   // elements; row j sits at element v4_tile_slot(j) of each slab, so the 64
@@ -695,16 +712,19 @@ __global__ void __launch_bounds__(256) score_forest_v4(
     if (ROWS_LDS) {
       __syncthreads();  // previous iteration's readers done
       // each thread stages its own rows: lanes with consecutive rows store
-      // consecutive words of a slab (conflict-free), rows are fetched in
-      // 16-byte pieces when their starts are 16-byte aligned
+      // consecutive words of a slab (conflict-free), row-major rows are
+      // fetched in 16-byte pieces when their starts are 16-byte aligned.
+      // A feature-major source (rs == 1) takes the element loop, where the
+      // lanes of a wave read consecutive addresses of one feature.
       constexpr int EPV = 16 / (int)sizeof(KT);
-      const bool vec = d % EPV == 0 && ((uintptr_t)X & 15) == 0;
+      const bool vec = cs == 1 && d % EPV == 0 && rs % EPV == 0 &&
+                       ((uintptr_t)X & 15) == 0;
 #pragma unroll
       for (int r = 0; r < RPT; ++r) {
         const int j = tid + r * 256;
         KT* dst = rows + v4_tile_slot<KT, RPT>(j);
         if (j < rows_here) {
-          const KT* src = X + (block_row0 + j) * d;
+          const KT* src = X + (block_row0 + j) * rs;
           if (vec) {
             for (int c = 0; c < d; c += EPV) {
               union { uint4 v; KT e[EPV]; } pc;
@@ -714,8 +734,13 @@ __global__ void __launch_bounds__(256) score_forest_v4(
                 dst[(c + k) * FS] = key_of_bits<KT>(pc.e[k]);
             }
           } else {
-            for (int c = 0; c < d; ++c)
-              dst[c * FS] = key_of_bits<KT>(src[c]);
+            if (PACKED) {
+              for (int c = 0; c < d; ++c)
+                dst[c * FS] = key_of_bits<KT>(src[c]);
+            } else {
+              for (int c = 0; c < d; ++c, src += cs)
+                dst[c * FS] = key_of_bits<KT>(*src);
+            }
           }
         } else {
           // tail block: rows past N are walked but never stored
@@ -786,7 +811,8 @@ __global__ void __launch_bounds__(256) score_forest_v4(
               // global fallback: the sentinel column does not exist in X,
               // so guard the leaf feature index.
               const int64_t my_row = block_row0 + tid + r * 256;
-              kraw[r][s] = (f < d && my_row < N) ? X[my_row * d + f] : KT{};
+              kraw[r][s] =
+                  (f < d && my_row < N) ? X[my_row * rs + f * cs] : KT{};
             }
           }
         }
@@ -846,6 +872,31 @@ __global__ void __launch_bounds__(256) score_forest_v4(
   }
 }
 
+// Entry points of the body above. score_forest_v4 serves every in-place
+// layout with runtime strides; score_forest_v4_packed has the argument list
+// the kernel had before it took strides and folds them to (d, 1).
+template <typename KT, int RPT, bool ROWS_LDS, int V4_ILP, bool NODES_LDS>
+__global__ void __launch_bounds__(256) score_forest_v4(
+    const KT* __restrict__ X, const int2* __restrict__ nodes,
+    const int32_t* __restrict__ ncnt, float* __restrict__ out, int64_t N,
+    int32_t d, int32_t Tpad, int32_t max_nodes, int32_t height_limit,
+    float fT, float c_norm, int32_t finalize, int64_t rs, int64_t cs) {
+  score_forest_v4_body<KT, RPT, ROWS_LDS, V4_ILP, NODES_LDS, false>(
+      X, nodes, ncnt, out, N, d, Tpad, max_nodes, height_limit, fT, c_norm,
+      finalize, rs, cs);
+}
+
+template <typename KT, int RPT, int V4_ILP>
+__global__ void __launch_bounds__(256) score_forest_v4_packed(
+    const KT* __restrict__ X, const int2* __restrict__ nodes,
+    const int32_t* __restrict__ ncnt, float* __restrict__ out, int64_t N,
+    int32_t d, int32_t Tpad, int32_t max_nodes, int32_t height_limit,
+    float fT, float c_norm, int32_t finalize) {
+  score_forest_v4_body<KT, RPT, true, V4_ILP, true, true>(
+      X, nodes, ncnt, out, N, d, Tpad, max_nodes, height_limit, fT, c_norm,
+      finalize, d, 1);
+}
+
 // ---------------------------------------------------------------------------
 // extended scoring, dense fast path (nnz == d): per visit a dense dot
 // row[0..d) . w[0..d). WLDS stages the live tree's weight matrix in LDS
@@ -881,13 +932,33 @@ __device__ __forceinline__ void row4(const float* p, int j4, float& x0,
   x0 = v.x; x1 = v.y; x2 = v.z; x3 = v.w;
 }
 
+// Row tile of a feature-major source (rs == 1) for the staging loops whose
+// flat index g -> (g / d, g % d) is coalesced only over packed rows: the row
+// index runs fastest, so the lanes of a wave read consecutive rows of one
+// column. X0 = X + block_row0; 256 threads; fn maps a loaded element to the
+// stored one. rows_here * d stays far below 2^31 (<= 512 rows, d <= 4095).
+template <typename T, typename Fn>
+__device__ __forceinline__ void stage_tile_feature_major(
+    T* rows, const T* X0, int rows_here, int d, int dpad, int64_t cs, int tid,
+    Fn fn) {
+  const uint32_t total = (uint32_t)rows_here * (uint32_t)d;
+  for (uint32_t g = tid; g < total; g += 256) {
+    const int c = (int)(g / (uint32_t)rows_here);
+    const int r = (int)(g % (uint32_t)rows_here);
+    rows[r * dpad + c] = fn(X0[r + (int64_t)c * cs]);
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ T stage_as_is(T v) { return v; }
+
 template <typename XT, bool ROWS_LDS, bool WLDS>
 __global__ void __launch_bounds__(256) score_extended_dense_kernel(
     const XT* __restrict__ X, const int2* __restrict__ nodes,
     const float* __restrict__ hw_g,  // [T][max_nodes][d] dense weights
     const int32_t* __restrict__ ncnt, float* __restrict__ out, int64_t N,
-    int32_t d, int32_t dpad, int32_t T, int32_t max_nodes, float fT,
-    float c_norm, int32_t finalize) {
+    int32_t d, int64_t rs, int64_t cs, int32_t dpad, int32_t T,
+    int32_t max_nodes, float fT, float c_norm, int32_t finalize) {
   const int tid = threadIdx.x;
   const int d4 = d >> 2;
 
@@ -902,10 +973,15 @@ __global__ void __launch_bounds__(256) score_extended_dense_kernel(
 
     if (ROWS_LDS) {
       __syncthreads();
-      const int64_t total = (int64_t)rows_here * d;
-      for (int64_t g = tid; g < total; g += 256) {
-        const int r = (int)(g / d), c = (int)(g % d);
-        rows[r * dpad + c] = X[(block_row0 + r) * d + c];
+      if (rs == 1) {
+        stage_tile_feature_major(rows, X + block_row0, rows_here, d, dpad, cs,
+                                 tid, stage_as_is<XT>);
+      } else {
+        const int64_t total = (int64_t)rows_here * d;
+        for (int64_t g = tid; g < total; g += 256) {
+          const int r = (int)(g / d), c = (int)(g % d);
+          rows[r * dpad + c] = X[(block_row0 + r) * rs + c * cs];
+        }
       }
       __syncthreads();
     }
@@ -944,10 +1020,11 @@ __global__ void __launch_bounds__(256) score_extended_dense_kernel(
             if (ROWS_LDS) {
               row4(my_lrow, j, x0, x1, x2, x3);
             } else {
-              x0 = load_feat<XT>(X, my_row * d + 4 * j);
-              x1 = load_feat<XT>(X, my_row * d + 4 * j + 1);
-              x2 = load_feat<XT>(X, my_row * d + 4 * j + 2);
-              x3 = load_feat<XT>(X, my_row * d + 4 * j + 3);
+              const int64_t xo = my_row * rs + 4 * j * cs;
+              x0 = load_feat<XT>(X, xo);
+              x1 = load_feat<XT>(X, xo + cs);
+              x2 = load_feat<XT>(X, xo + 2 * cs);
+              x3 = load_feat<XT>(X, xo + 3 * cs);
             }
             ax = __fadd_rn(ax, __fmul_rn(w.x, x0));
             ay = __fadd_rn(ay, __fmul_rn(w.y, x1));
@@ -1016,11 +1093,11 @@ __device__ __forceinline__ float load_row_f32<uint32_t>(const uint32_t* X,
 template <typename KT, int D>
 struct RowReg {
   float v[D];
-  __device__ __forceinline__ void load(const KT* X, int64_t base, int d,
-                                       bool ok) {
+  __device__ __forceinline__ void load(const KT* X, int64_t base, int64_t cs,
+                                       int d, bool ok) {
 #pragma unroll
     for (int j = 0; j < D; ++j)
-      v[j] = (ok && j < d) ? load_row_f32<KT>(X, base + j) : 0.f;
+      v[j] = (ok && j < d) ? load_row_f32<KT>(X, base + j * cs) : 0.f;
   }
   __device__ __forceinline__ float get(int j) const { return v[j]; }
 };
@@ -1035,9 +1112,9 @@ __global__ void __launch_bounds__(EIFD_THREADS,
     const float* __restrict__ values,   // [T][max_nodes] leaf value+depth
     const float* __restrict__ hw,       // [T][max_nodes][D] PADDED dense w
     const int32_t* __restrict__ ncnt,   // [T]
-    float* __restrict__ out, int64_t N, int32_t d, int32_t T,
-    int32_t max_nodes, int32_t height_limit, float fT, float c_norm,
-    int32_t finalize) {
+    float* __restrict__ out, int64_t N, int32_t d, int64_t rs, int64_t cs,
+    int32_t T, int32_t max_nodes, int32_t height_limit, float fT,
+    float c_norm, int32_t finalize) {
   const int tid = threadIdx.x;
   const int rows_per_iter = RPT * EIFD_THREADS;
   const int DW4 = D / 4 + 1;  // LDS weight-row stride in float4s
@@ -1052,7 +1129,7 @@ __global__ void __launch_bounds__(EIFD_THREADS,
 #pragma unroll
     for (int r = 0; r < RPT; ++r) {
       const int64_t my_row = block_row0 + tid + r * EIFD_THREADS;
-      row[r].load(X, my_row * d, d, my_row < N);
+      row[r].load(X, my_row * rs, cs, d, my_row < N);
     }
 
     float psum[RPT];
@@ -1183,9 +1260,9 @@ score_extended_dense_v3(
     const float* __restrict__ values,   // [T][max_nodes] leaf value+depth
     const uint32_t* __restrict__ hwp,   // [T][max_nodes][D/2] packed bf16 pairs
     const int32_t* __restrict__ ncnt,   // [T]
-    float* __restrict__ out, int64_t N, int32_t d, int32_t T,
-    int32_t max_nodes, int32_t height_limit, float fT, float c_norm,
-    int32_t finalize) {
+    float* __restrict__ out, int64_t N, int32_t d, int64_t rs, int64_t cs,
+    int32_t T, int32_t max_nodes, int32_t height_limit, float fT,
+    float c_norm, int32_t finalize) {
   const int tid = threadIdx.x;
   const int rows_per_iter = RPT * EIFD_THREADS;
   constexpr int PW4 = D / 8 + 1;  // LDS weight-row stride in uint4s
@@ -1201,11 +1278,12 @@ score_extended_dense_v3(
     for (int r = 0; r < RPT; ++r) {
       const int64_t my_row = block_row0 + tid + r * EIFD_THREADS;
       const bool ok = my_row < N;
-      const int64_t base = my_row * d;
+      const int64_t base = my_row * rs;
 #pragma unroll
       for (int j2 = 0; j2 < D / 2; ++j2) {
-        const uint32_t lo = (ok && 2 * j2 < d) ? X[base + 2 * j2] : 0u;
-        const uint32_t hi = (ok && 2 * j2 + 1 < d) ? X[base + 2 * j2 + 1] : 0u;
+        const uint32_t lo = (ok && 2 * j2 < d) ? X[base + 2 * j2 * cs] : 0u;
+        const uint32_t hi =
+            (ok && 2 * j2 + 1 < d) ? X[base + (2 * j2 + 1) * cs] : 0u;
         xp[r][j2] = lo | (hi << 16);
       }
     }
@@ -1329,9 +1407,9 @@ __global__ void __launch_bounds__(256) score_extended_dense_nonfinite_rows(
     const float* __restrict__ values,   // [T][max_nodes] leaf value+depth
     const void* __restrict__ wts,       // f32 [T][max_nodes][D] or packed
                                         // bf16 pairs u32 [T][max_nodes][D/2]
-    float* __restrict__ out, int64_t N, int32_t d, int32_t D, int32_t T,
-    int32_t max_nodes, int32_t height_limit, float fT, float c_norm,
-    int32_t finalize) {
+    float* __restrict__ out, int64_t N, int32_t d, int64_t rs, int64_t cs,
+    int32_t D, int32_t T, int32_t max_nodes, int32_t height_limit, float fT,
+    float c_norm, int32_t finalize) {
   __shared__ int flagged[256];
   const int tid = threadIdx.x;
   for (int64_t block_row0 = (int64_t)blockIdx.x * 256; block_row0 < N;
@@ -1341,9 +1419,19 @@ __global__ void __launch_bounds__(256) score_extended_dense_nonfinite_rows(
     flagged[tid] = 0;
     __syncthreads();
     const int total = rows_here * d;
-    for (int g = tid; g < total; g += 256)
-      if (nonfinite_bits(X[block_row0 * d + g]))
-        flagged[g / d] = 1;  // every writer stores the same value
+    if (rs == 1) {  // feature-major: lanes scan consecutive rows of a column
+      for (int g = tid; g < total; g += 256) {
+        const int c = g / rows_here, r = g % rows_here;
+        if (nonfinite_bits(X[block_row0 + r + (int64_t)c * cs]))
+          flagged[r] = 1;  // every writer stores the same value
+      }
+    } else {
+      for (int g = tid; g < total; g += 256) {
+        const int r = g / d, c = g % d;
+        if (nonfinite_bits(X[(block_row0 + r) * rs + c * cs]))
+          flagged[r] = 1;  // every writer stores the same value
+      }
+    }
     __syncthreads();
     if (tid >= rows_here || !flagged[tid]) continue;
 
@@ -1367,7 +1455,8 @@ __global__ void __launch_bounds__(256) score_extended_dense_nonfinite_rows(
             w = ((const float*)wts)[(tbase + cur) * D + j];
           }
           dot = __fadd_rn(dot,
-                          __fmul_rn(w, load_row_f32<KT>(X, my_row * d + j)));
+                          __fmul_rn(w, load_row_f32<KT>(X,
+                          my_row * rs + j * cs)));
         }
         cur = (dot < __int_as_float(nd.y)) ? cur + 1 : right;
       }
@@ -1400,8 +1489,9 @@ __global__ void __launch_bounds__(256) score_extended_sparse_v2(
     const int32_t* __restrict__ hidx_g, // [T][max_nodes][NNZ]
     const float* __restrict__ hw_g,     // [T][max_nodes][NNZ]
     const int32_t* __restrict__ ncnt, float* __restrict__ out, int64_t N,
-    int32_t d, int32_t dpad, int32_t T, int32_t max_nodes,
-    int32_t height_limit, float fT, float c_norm, int32_t finalize) {
+    int32_t d, int64_t rs, int64_t cs, int32_t dpad, int32_t T,
+    int32_t max_nodes, int32_t height_limit, float fT, float c_norm,
+    int32_t finalize) {
   const int tid = threadIdx.x;
   const int rows_per_iter = RPT * 256;
 
@@ -1415,11 +1505,14 @@ __global__ void __launch_bounds__(256) score_extended_sparse_v2(
        block_row0 += (int64_t)gridDim.x * rows_per_iter) {
     const int rows_here = (int)min((int64_t)rows_per_iter, N - block_row0);
     __syncthreads();  // previous iteration's readers done
-    {
+    if (rs == 1) {
+      stage_tile_feature_major(rows, X + block_row0, rows_here, d, dpad, cs,
+                               tid, stage_as_is<KT>);
+    } else {
       const int64_t total = (int64_t)rows_here * d;
       for (int64_t g = tid; g < total; g += 256) {
         const int r = (int)(g / (uint32_t)d), c = (int)(g % (uint32_t)d);
-        rows[r * dpad + c] = X[(block_row0 + r) * d + c];
+        rows[r * dpad + c] = X[(block_row0 + r) * rs + c * cs];
       }
     }
     __syncthreads();
@@ -1515,8 +1608,8 @@ __global__ void __launch_bounds__(256) score_extended_forest_kernel(
     const int32_t* __restrict__ hidx_g,  // [T][max_nodes][nnz]
     const float* __restrict__ hw_g,      // [T][max_nodes][nnz]
     const int32_t* __restrict__ ncnt, float* __restrict__ out, int64_t N,
-    int32_t d, int32_t T, int32_t max_nodes, int32_t nnz, float fT,
-    float c_norm, int32_t finalize) {
+    int32_t d, int64_t rs, int64_t cs, int32_t T, int32_t max_nodes,
+    int32_t nnz, float fT, float c_norm, int32_t finalize) {
   const int tid = threadIdx.x;
   const int dpad = row_stride<XT>(d);
 
@@ -1532,10 +1625,15 @@ __global__ void __launch_bounds__(256) score_extended_forest_kernel(
 
     if (ROWS_LDS) {
       __syncthreads();
-      const int64_t total = (int64_t)rows_here * d;
-      for (int64_t g = tid; g < total; g += 256) {
-        const int r = (int)(g / d), c = (int)(g % d);
-        rows[r * dpad + c] = X[(block_row0 + r) * d + c];
+      if (rs == 1) {
+        stage_tile_feature_major(rows, X + block_row0, rows_here, d, dpad, cs,
+                                 tid, stage_as_is<XT>);
+      } else {
+        const int64_t total = (int64_t)rows_here * d;
+        for (int64_t g = tid; g < total; g += 256) {
+          const int r = (int)(g / d), c = (int)(g % d);
+          rows[r * dpad + c] = X[(block_row0 + r) * rs + c * cs];
+        }
       }
       __syncthreads();
     }
@@ -1575,7 +1673,7 @@ __global__ void __launch_bounds__(256) score_extended_forest_kernel(
           for (int j = 0; j < nnz; ++j) {
             const float xv = ROWS_LDS
                                  ? cvt_feat(my_lrow[ci[j]])
-                                 : load_feat<XT>(X, my_row * d + ci[j]);
+                                 : load_feat<XT>(X, my_row * rs + ci[j] * cs);
             dot = __fadd_rn(dot, __fmul_rn(cw[j], xv));
           }
           cur = (dot < __int_as_float(nd.y)) ? cur + 1 : pn_right(nd.x);
@@ -1614,9 +1712,9 @@ template <typename KT>
 __global__ void __launch_bounds__(256) score_forest_wide(
     const KT* __restrict__ X,          // raw bf16/fp16/f32 bits [N][d]
     const int4* __restrict__ nodes,    // [T][max_nodes] {feat, right, w, 0}
-    float* __restrict__ out, int64_t N, int32_t d, int32_t T,
-    int64_t max_nodes, int32_t height_limit, float fT, float c_norm,
-    int32_t finalize) {
+    float* __restrict__ out, int64_t N, int32_t d, int64_t rs, int64_t cs,
+    int32_t T, int64_t max_nodes, int32_t height_limit, float fT,
+    float c_norm, int32_t finalize) {
   for (int64_t my_row = (int64_t)blockIdx.x * 256 + threadIdx.x; my_row < N;
        my_row += (int64_t)gridDim.x * 256) {
     float psum = 0.f;
@@ -1627,7 +1725,7 @@ __global__ void __launch_bounds__(256) score_forest_wide(
         const int4 nd = base[cur];
         if (nd.y != cur) {  // leaves self-loop (right == own id)
           const uint32_t x =
-              widen_key(key_of_bits<KT>(X[my_row * d + nd.x]));
+              widen_key(key_of_bits<KT>(X[my_row * rs + nd.x * cs]));
           cur = (x < (uint32_t)nd.z) ? cur + 1 : nd.y;
         }
       }
@@ -1650,8 +1748,8 @@ __global__ void __launch_bounds__(256) score_extended_wide(
     const XT* __restrict__ X, const int4* __restrict__ nodes,
     const int32_t* __restrict__ hidx_g,  // [T][max_nodes][nnz]
     const float* __restrict__ hw_g,      // [T][max_nodes][nnz]
-    float* __restrict__ out, int64_t N, int32_t d, int32_t T,
-    int64_t max_nodes, int32_t nnz, float fT, float c_norm,
+    float* __restrict__ out, int64_t N, int32_t d, int64_t rs, int64_t cs,
+    int32_t T, int64_t max_nodes, int32_t nnz, float fT, float c_norm,
     int32_t finalize) {
   for (int64_t my_row = (int64_t)blockIdx.x * 256 + threadIdx.x; my_row < N;
        my_row += (int64_t)gridDim.x * 256) {
@@ -1671,7 +1769,7 @@ __global__ void __launch_bounds__(256) score_extended_wide(
         const int32_t* ci = hidx_g + hbase + (int64_t)cur * nnz;
         const float* cw = hw_g + hbase + (int64_t)cur * nnz;
         for (int j = 0; j < nnz; ++j) {
-          const float xv = load_feat<XT>(X, my_row * d + ci[j]);
+          const float xv = load_feat<XT>(X, my_row * rs + ci[j] * cs);
           dot = __fadd_rn(dot, __fmul_rn(cw[j], xv));
         }
         cur = (dot < __int_as_float(nd.z)) ? cur + 1 : nd.y;
@@ -1723,7 +1821,14 @@ __device__ __forceinline__ float div32_exact(float a, float b) {
   return (float)((double)a / (double)b);
 }
 
-template <typename KT, int RPT, bool ACC_LDS, bool ROWS_LDS, bool NODES_LDS>
+// PACKED: the strides fold to (d, 1); instantiated only for mode 0
+// (accumulators, rows and nodes in LDS) and used for packed rows. The stride
+// arguments come last so that the arguments before them keep their kernarg
+// offsets: the PACKED instantiations then compile to the instruction stream
+// the kernel had before it took strides, register names aside
+// (profiles/strided.md).
+template <typename KT, int RPT, bool ACC_LDS, bool ROWS_LDS, bool NODES_LDS,
+          bool PACKED>
 __global__ void __launch_bounds__(256) explain_forest_kernel(
     const KT* __restrict__ X,          // raw bf16/fp16/f32 bits [N][d]
     const int4* __restrict__ nodes,    // [T][max_nodes] explain records
@@ -1731,9 +1836,11 @@ __global__ void __launch_bounds__(256) explain_forest_kernel(
     float* __restrict__ out,           // [N][d] (pre-zeroed when !ACC_LDS)
     int64_t N, int32_t d, int32_t dpad, int32_t astride, int32_t T,
     int32_t max_nodes, int32_t tps, int32_t height_limit, float fT,
-    int32_t finalize) {
+    int32_t finalize, int64_t rs_, int64_t cs_) {
   const int tid = threadIdx.x;
   const int rows_per_iter = RPT * 256;
+  const int64_t rs = PACKED ? (int64_t)d : rs_;
+  const int64_t cs = PACKED ? (int64_t)1 : cs_;
 
   int4* tlds = (int4*)smem;  // [tps * max_nodes] when NODES_LDS
   float* acc = (float*)(tlds + (NODES_LDS ? tps * max_nodes : 0));
@@ -1745,10 +1852,16 @@ __global__ void __launch_bounds__(256) explain_forest_kernel(
 
     __syncthreads();  // previous tile's flush / readers done
     if (ROWS_LDS) {
-      const int64_t total = (int64_t)rows_here * d;
-      for (int64_t g = tid; g < total; g += 256) {
-        const int r = (int)(g / (uint32_t)d), c = (int)(g % (uint32_t)d);
-        rows[r * dpad + c] = key_of_bits<KT>(X[(block_row0 + r) * d + c]);
+      if (!PACKED && rs == 1) {
+        stage_tile_feature_major(rows, X + block_row0, rows_here, d, dpad, cs,
+                                 tid, key_of_bits<KT>);
+      } else {
+        const int64_t total = (int64_t)rows_here * d;
+        for (int64_t g = tid; g < total; g += 256) {
+          const int r = (int)(g / (uint32_t)d), c = (int)(g % (uint32_t)d);
+          rows[r * dpad + c] =
+              key_of_bits<KT>(X[(block_row0 + r) * rs + c * cs]);
+        }
       }
       for (int r = tid; r < rows_per_iter; r += 256)
         rows[r * dpad + d] = key_sentinel<KT>();  // leaf sentinel column
@@ -1799,7 +1912,8 @@ __global__ void __launch_bounds__(256) explain_forest_kernel(
             } else {
               // the sentinel column does not exist in X: guard it
               x[r] = (f < d && my_row[r] < N)
-                         ? widen_key(key_of_bits<KT>(X[my_row[r] * d + f]))
+                         ? widen_key(key_of_bits<KT>(
+                               X[my_row[r] * rs + f * cs]))
                          : 0xFFFFFFFFu;
             }
           }
@@ -1854,8 +1968,8 @@ __global__ void __launch_bounds__(256) explain_extended_kernel(
     const float* __restrict__ dl_g,      // [T][max_nodes][nnz]
     const float* __restrict__ dr_g,      // [T][max_nodes][nnz]
     float* __restrict__ out,             // [N][d] pre-zeroed
-    int64_t N, int32_t d, int32_t T, int32_t max_nodes, int32_t nnz,
-    float fT, int32_t finalize) {
+    int64_t N, int32_t d, int64_t rs, int64_t cs, int32_t T,
+    int32_t max_nodes, int32_t nnz, float fT, int32_t finalize) {
   for (int64_t my_row = (int64_t)blockIdx.x * 256 + threadIdx.x; my_row < N;
        my_row += (int64_t)gridDim.x * 256) {
     float* orow = out + my_row * d;
@@ -1871,7 +1985,7 @@ __global__ void __launch_bounds__(256) explain_extended_kernel(
         const float* cw = hw_g + hoff;
         float dot = 0.f;
         for (int j = 0; j < nnz; ++j) {
-          const float xv = load_feat<XT>(X, my_row * d + ci[j]);
+          const float xv = load_feat<XT>(X, my_row * rs + ci[j] * cs);
           dot = __fadd_rn(dot, __fmul_rn(cw[j], xv));
         }
         const bool left = dot < __int_as_float(nd.y);
@@ -1906,6 +2020,7 @@ static inline void raise_lds(const void* func, size_t bytes) {
 
 void launch_bag_gather(RowDtype dt, const void* X, const int64_t* bag_idx,
                        float* bags, int64_t T, int64_t n, int64_t d,
+                       int64_t rs, int64_t cs,
                        hipStream_t stream) {
   int64_t total = T * n * d;
   int threads = 256;
@@ -1914,13 +2029,15 @@ void launch_bag_gather(RowDtype dt, const void* X, const int64_t* bag_idx,
   if (blocks < 1) blocks = 1;
   if (dt == ROW_BF16)
     hipLaunchKernelGGL(bag_gather_kernel<uint16_t>, dim3(blocks), dim3(threads),
-                       0, stream, (const uint16_t*)X, bag_idx, bags, T, n, d);
+                       0, stream, (const uint16_t*)X, bag_idx, bags, T, n, d,
+                       rs, cs);
   else if (dt == ROW_F16)
     hipLaunchKernelGGL(bag_gather_kernel<f16_t>, dim3(blocks), dim3(threads),
-                       0, stream, (const f16_t*)X, bag_idx, bags, T, n, d);
+                       0, stream, (const f16_t*)X, bag_idx, bags, T, n, d, rs,
+                       cs);
   else
     hipLaunchKernelGGL(bag_gather_kernel<float>, dim3(blocks), dim3(threads), 0,
-                       stream, (const float*)X, bag_idx, bags, T, n, d);
+                       stream, (const float*)X, bag_idx, bags, T, n, d, rs, cs);
 }
 
 void launch_build_forest(const float* bags, const int32_t* feat_sub,
@@ -1966,25 +2083,36 @@ void launch_v4_level_order(const void* nodes, const int32_t* ncount,
 void launch_score_forest(RowDtype dt, int rpt, bool rows_lds, bool nodes_lds,
                          int ilp, const void* X, const void* nodes,
                          const int32_t* ncount, float* out, int64_t N,
-                         int32_t d, int32_t Tpad,
+                         int32_t d, int64_t rs, int64_t cs, int32_t Tpad,
                          int32_t max_nodes, int32_t height_limit, float fT,
                          float c_norm, int finalize, size_t lds, int blocks,
                          hipStream_t stream) {
+  // packed rows take the packed entry point where one exists: rows and
+  // nodes staged in LDS at ILP 4. The global-X walk, the deep-forest node
+  // walk and the other ILPs have one entry point for every layout.
+  const bool packed = rs == d && cs == 1;
+#define LS1(KT, RPT, RL, TI, NL)                                              \
+  do {                                                                        \
+    raise_lds((const void*)score_forest_v4<KT, RPT, RL, TI, NL>, lds);        \
+    hipLaunchKernelGGL((score_forest_v4<KT, RPT, RL, TI, NL>), dim3(blocks),  \
+                       dim3(256), lds, stream, (const KT*)X,                  \
+                       (const int2*)nodes, ncount, out, N, d, Tpad,           \
+                       max_nodes, height_limit, fT, c_norm, finalize, rs,     \
+                       cs);                                                   \
+  } while (0)
+#define LS1P(KT, RPT)                                                         \
+  do {                                                                        \
+    raise_lds((const void*)score_forest_v4_packed<KT, RPT, 4>, lds);          \
+    hipLaunchKernelGGL((score_forest_v4_packed<KT, RPT, 4>), dim3(blocks),    \
+                       dim3(256), lds, stream, (const KT*)X,                  \
+                       (const int2*)nodes, ncount, out, N, d, Tpad,           \
+                       max_nodes, height_limit, fT, c_norm, finalize);        \
+  } while (0)
 #define LS(KT, RPT, RL, TI)                                                   \
   do {                                                                        \
-    if (nodes_lds) {                                                          \
-      raise_lds((const void*)score_forest_v4<KT, RPT, RL, TI, true>, lds);    \
-      hipLaunchKernelGGL((score_forest_v4<KT, RPT, RL, TI, true>),            \
-                         dim3(blocks), dim3(256), lds, stream, (const KT*)X,  \
-                         (const int2*)nodes, ncount, out, N, d, Tpad,         \
-                         max_nodes, height_limit, fT, c_norm, finalize);      \
-    } else {                                                                  \
-      raise_lds((const void*)score_forest_v4<KT, RPT, RL, TI, false>, lds);   \
-      hipLaunchKernelGGL((score_forest_v4<KT, RPT, RL, TI, false>),           \
-                         dim3(blocks), dim3(256), lds, stream, (const KT*)X,  \
-                         (const int2*)nodes, ncount, out, N, d, Tpad,         \
-                         max_nodes, height_limit, fT, c_norm, finalize);      \
-    }                                                                         \
+    if (nodes_lds && packed && RL && TI == 4) LS1P(KT, RPT);                  \
+    else if (nodes_lds) LS1(KT, RPT, RL, TI, true);                           \
+    else LS1(KT, RPT, RL, TI, false);                                         \
   } while (0)
 #define LS_ILP(KT, RPT, RL)                                                   \
   do {                                                                        \
@@ -2007,21 +2135,25 @@ void launch_score_forest(RowDtype dt, int rpt, bool rows_lds, bool nodes_lds,
   }
 #undef LS_ILP
 #undef LS
+#undef LS1P
+#undef LS1
 }
 
 void launch_score_extended_dense(RowDtype dt, bool rows_lds, bool wlds,
                                  const void* X, const void* nodes,
                                  const float* hw, const int32_t* ncount,
-                                 float* out, int64_t N, int32_t d,
-                                 int32_t dpad, int32_t T, int32_t max_nodes,
-                                 float fT, float c_norm, int finalize,
-                                 size_t lds, int blocks, hipStream_t stream) {
+                                 float* out, int64_t N, int32_t d, int64_t rs,
+                                 int64_t cs, int32_t dpad, int32_t T,
+                                 int32_t max_nodes, float fT, float c_norm,
+                                 int finalize, size_t lds, int blocks,
+                                 hipStream_t stream) {
 #define LSD(XT, RL, WL)                                                       \
   do {                                                                        \
     raise_lds((const void*)score_extended_dense_kernel<XT, RL, WL>, lds);     \
     hipLaunchKernelGGL((score_extended_dense_kernel<XT, RL, WL>),             \
                        dim3(blocks), dim3(256), lds, stream, (const XT*)X,    \
-                       (const int2*)nodes, hw, ncount, out, N, d, dpad, T,    \
+                       (const int2*)nodes, hw, ncount, out, N, d, rs, cs,     \
+                       dpad, T,                                               \
                        max_nodes, fT, c_norm, finalize);                      \
   } while (0)
   if (dt == ROW_BF16) {
@@ -2047,6 +2179,7 @@ void launch_score_extended_dense_v2(RowDtype dt, int D, const void* X,
                                     const void* nodes, const float* values,
                                     const float* hw, const int32_t* ncount,
                                     float* out, int64_t N, int32_t d,
+                                    int64_t rs, int64_t cs,
                                     int32_t T, int32_t max_nodes,
                                     int32_t height_limit, float fT,
                                     float c_norm, int finalize, size_t lds,
@@ -2056,7 +2189,8 @@ void launch_score_extended_dense_v2(RowDtype dt, int D, const void* X,
     raise_lds((const void*)score_extended_dense_v2<KT, DD, RR>, lds);         \
     hipLaunchKernelGGL((score_extended_dense_v2<KT, DD, RR>), dim3(blocks),   \
                        dim3(EIFD_THREADS), lds, stream, (const KT*)X,         \
-                       (const int2*)nodes, values, hw, ncount, out, N, d, T,  \
+                       (const int2*)nodes, values, hw, ncount, out, N, d,     \
+                       rs, cs, T,                                             \
                        max_nodes, height_limit, fT, c_norm, finalize);        \
   } while (0)
   // D=32 runs RPT=1: 2 rows/thread would spill past the 128-VGPR budget
@@ -2081,44 +2215,49 @@ void launch_score_extended_dense_v2(RowDtype dt, int D, const void* X,
 }
 
 void launch_score_forest_wide(RowDtype dt, const void* X, const void* nodes,
-                              float* out, int64_t N, int32_t d, int32_t T,
+                              float* out, int64_t N, int32_t d, int64_t rs,
+                              int64_t cs, int32_t T,
                               int64_t max_nodes, int32_t height_limit,
                               float fT, float c_norm, int finalize,
                               int blocks, hipStream_t stream) {
   if (dt == ROW_BF16)
     hipLaunchKernelGGL((score_forest_wide<uint16_t>), dim3(blocks), dim3(256),
                        0, stream, (const uint16_t*)X, (const int4*)nodes, out,
-                       N, d, T, max_nodes, height_limit, fT, c_norm, finalize);
+                       N, d, rs, cs, T, max_nodes, height_limit, fT, c_norm,
+                       finalize);
   else if (dt == ROW_F16)
     hipLaunchKernelGGL((score_forest_wide<f16_t>), dim3(blocks), dim3(256),
                        0, stream, (const f16_t*)X, (const int4*)nodes, out,
-                       N, d, T, max_nodes, height_limit, fT, c_norm, finalize);
+                       N, d, rs, cs, T, max_nodes, height_limit, fT, c_norm,
+                       finalize);
   else
     hipLaunchKernelGGL((score_forest_wide<uint32_t>), dim3(blocks), dim3(256),
                        0, stream, (const uint32_t*)X, (const int4*)nodes, out,
-                       N, d, T, max_nodes, height_limit, fT, c_norm, finalize);
+                       N, d, rs, cs, T, max_nodes, height_limit, fT, c_norm,
+                       finalize);
 }
 
 void launch_score_extended_wide(RowDtype dt, const void* X, const void* nodes,
                                 const int32_t* hidx, const float* hw,
-                                float* out, int64_t N, int32_t d, int32_t T,
+                                float* out, int64_t N, int32_t d, int64_t rs,
+                                int64_t cs, int32_t T,
                                 int64_t max_nodes, int32_t nnz, float fT,
                                 float c_norm, int finalize, int blocks,
                                 hipStream_t stream) {
   if (dt == ROW_BF16)
     hipLaunchKernelGGL((score_extended_wide<uint16_t>), dim3(blocks),
                        dim3(256), 0, stream, (const uint16_t*)X,
-                       (const int4*)nodes, hidx, hw, out, N, d, T, max_nodes,
-                       nnz, fT, c_norm, finalize);
+                       (const int4*)nodes, hidx, hw, out, N, d, rs, cs, T,
+                       max_nodes, nnz, fT, c_norm, finalize);
   else if (dt == ROW_F16)
     hipLaunchKernelGGL((score_extended_wide<f16_t>), dim3(blocks),
                        dim3(256), 0, stream, (const f16_t*)X,
-                       (const int4*)nodes, hidx, hw, out, N, d, T, max_nodes,
-                       nnz, fT, c_norm, finalize);
+                       (const int4*)nodes, hidx, hw, out, N, d, rs, cs, T,
+                       max_nodes, nnz, fT, c_norm, finalize);
   else
     hipLaunchKernelGGL((score_extended_wide<float>), dim3(blocks), dim3(256),
                        0, stream, (const float*)X, (const int4*)nodes, hidx,
-                       hw, out, N, d, T, max_nodes, nnz, fT, c_norm,
+                       hw, out, N, d, rs, cs, T, max_nodes, nnz, fT, c_norm,
                        finalize);
 }
 
@@ -2126,7 +2265,8 @@ void launch_score_extended_dense_v3(int D, bool rpt2, const void* X,
                                     const void* nodes, const float* values,
                                     const uint32_t* hwp,
                                     const int32_t* ncount, float* out,
-                                    int64_t N, int32_t d, int32_t T,
+                                    int64_t N, int32_t d, int64_t rs,
+                                    int64_t cs, int32_t T,
                                     int32_t max_nodes, int32_t height_limit,
                                     float fT, float c_norm, int finalize,
                                     size_t lds, int blocks,
@@ -2136,7 +2276,8 @@ void launch_score_extended_dense_v3(int D, bool rpt2, const void* X,
     raise_lds((const void*)score_extended_dense_v3<DD, RR>, lds);             \
     hipLaunchKernelGGL((score_extended_dense_v3<DD, RR>), dim3(blocks),       \
                        dim3(EIFD_THREADS), lds, stream, (const uint16_t*)X,   \
-                       (const int2*)nodes, values, hwp, ncount, out, N, d, T, \
+                       (const int2*)nodes, values, hwp, ncount, out, N, d,    \
+                       rs, cs, T,                                             \
                        max_nodes, height_limit, fT, c_norm, finalize);        \
   } while (0)
   if (D == 8) LSD3(8, 2);
@@ -2151,12 +2292,14 @@ void launch_score_extended_dense_v3(int D, bool rpt2, const void* X,
 void launch_score_extended_dense_nonfinite_rows(
     RowDtype dt, bool packed_w, const void* X, const void* nodes,
     const float* values, const void* wts, float* out, int64_t N, int32_t d,
+    int64_t rs, int64_t cs,
     int32_t D, int32_t T, int32_t max_nodes, int32_t height_limit, float fT,
     float c_norm, int finalize, int blocks, hipStream_t stream) {
 #define LNF(KT, PW)                                                           \
   hipLaunchKernelGGL((score_extended_dense_nonfinite_rows<KT, PW>),           \
                      dim3(blocks), dim3(256), 0, stream, (const KT*)X,        \
-                     (const int2*)nodes, values, wts, out, N, d, D, T,        \
+                     (const int2*)nodes, values, wts, out, N, d, rs, cs, D,   \
+                     T,                                                       \
                      max_nodes, height_limit, fT, c_norm, finalize)
   // v3 (packed weights) takes bf16 rows only
   if (dt == ROW_BF16) {
@@ -2173,7 +2316,8 @@ void launch_score_extended_sparse_v2(RowDtype dt, int nnz, const void* X,
                                      const void* nodes, const float* values,
                                      const int32_t* hidx, const float* hw,
                                      const int32_t* ncount, float* out,
-                                     int64_t N, int32_t d, int32_t dpad,
+                                     int64_t N, int32_t d, int64_t rs,
+                                     int64_t cs, int32_t dpad,
                                      int32_t T, int32_t max_nodes,
                                      int32_t height_limit, float fT,
                                      float c_norm, int finalize, size_t lds,
@@ -2184,8 +2328,8 @@ void launch_score_extended_sparse_v2(RowDtype dt, int nnz, const void* X,
     hipLaunchKernelGGL((score_extended_sparse_v2<KT, NZ, 2>), dim3(blocks),   \
                        dim3(256), lds, stream, (const KT*)X,                  \
                        (const int2*)nodes, values, hidx, hw, ncount, out, N,  \
-                       d, dpad, T, max_nodes, height_limit, fT, c_norm,       \
-                       finalize);                                             \
+                       d, rs, cs, dpad, T, max_nodes, height_limit, fT,       \
+                       c_norm, finalize);                                     \
   } while (0)
 #define LSS2_ALL(KT)                                                          \
   do {                                                                        \
@@ -2208,7 +2352,8 @@ void launch_score_extended_forest(RowDtype dt, bool rows_lds, bool hyper_lds,
                                   bool nodes_lds, const void* X,
                                   const void* nodes, const int32_t* hidx,
                                   const float* hw, const int32_t* ncount,
-                                  float* out, int64_t N, int32_t d, int32_t T,
+                                  float* out, int64_t N, int32_t d, int64_t rs,
+                                  int64_t cs, int32_t T,
                                   int32_t max_nodes, int32_t nnz, float fT,
                                   float c_norm, int finalize, size_t lds,
                                   int blocks, hipStream_t stream) {
@@ -2219,14 +2364,17 @@ void launch_score_extended_forest(RowDtype dt, bool rows_lds, bool hyper_lds,
                 lds);                                                         \
       hipLaunchKernelGGL((score_extended_forest_kernel<XT, RL, HL, true>),    \
                          dim3(blocks), dim3(256), lds, stream, (const XT*)X,  \
-                         (const int2*)nodes, hidx, hw, ncount, out, N, d, T,  \
+                         (const int2*)nodes, hidx, hw, ncount, out, N, d,     \
+                         rs, cs, T,                                           \
                          max_nodes, nnz, fT, c_norm, finalize);               \
     } else {                                                                  \
-      raise_lds((const void*)score_extended_forest_kernel<XT, RL, HL, false>, \
+      raise_lds((const void*)score_extended_forest_kernel<XT, RL, HL,         \
+      false>,                                                                 \
                 lds);                                                         \
       hipLaunchKernelGGL((score_extended_forest_kernel<XT, RL, HL, false>),   \
                          dim3(blocks), dim3(256), lds, stream, (const XT*)X,  \
-                         (const int2*)nodes, hidx, hw, ncount, out, N, d, T,  \
+                         (const int2*)nodes, hidx, hw, ncount, out, N, d,     \
+                         rs, cs, T,                                           \
                          max_nodes, nnz, fT, c_norm, finalize);               \
     }                                                                         \
   } while (0)
@@ -2254,17 +2402,27 @@ void launch_score_extended_forest(RowDtype dt, bool rows_lds, bool hyper_lds,
 void launch_explain_forest(RowDtype dt, int mode, int rpt, bool nodes_lds,
                            const void* X, const void* nodes,
                            const int32_t* ncount, float* out, int64_t N,
-                           int32_t d, int32_t dpad, int32_t astride,
-                           int32_t T, int32_t max_nodes, int32_t tps,
-                           int32_t height_limit, float fT, int finalize,
-                           size_t lds, int blocks, hipStream_t stream) {
-#define LX(KT, RPT, AL, RL, NL)                                               \
+                           int32_t d, int64_t rs, int64_t cs, int32_t dpad,
+                           int32_t astride, int32_t T, int32_t max_nodes,
+                           int32_t tps, int32_t height_limit, float fT,
+                           int finalize, size_t lds, int blocks,
+                           hipStream_t stream) {
+  // packed rows take the PACKED instantiation of mode 0 with staged nodes
+  const bool packed = rs == d && cs == 1;
+#define LX1(KT, RPT, AL, RL, NL, PK)                                          \
   do {                                                                        \
-    raise_lds((const void*)explain_forest_kernel<KT, RPT, AL, RL, NL>, lds);  \
-    hipLaunchKernelGGL((explain_forest_kernel<KT, RPT, AL, RL, NL>),          \
+    raise_lds((const void*)explain_forest_kernel<KT, RPT, AL, RL, NL, PK>,    \
+              lds);                                                           \
+    hipLaunchKernelGGL((explain_forest_kernel<KT, RPT, AL, RL, NL, PK>),      \
                        dim3(blocks), dim3(256), lds, stream, (const KT*)X,    \
                        (const int4*)nodes, ncount, out, N, d, dpad, astride,  \
-                       T, max_nodes, tps, height_limit, fT, finalize);        \
+                       T, max_nodes, tps, height_limit, fT, finalize, rs,     \
+                       cs);                                                   \
+  } while (0)
+#define LX(KT, RPT, AL, RL, NL)                                               \
+  do {                                                                        \
+    if (packed) LX1(KT, RPT, AL, RL, NL, (AL && RL && NL));                   \
+    else LX1(KT, RPT, AL, RL, NL, false);                                     \
   } while (0)
 #define LX_MODE(KT, NL)                                                       \
   do {                                                                        \
@@ -2282,29 +2440,31 @@ void launch_explain_forest(RowDtype dt, int mode, int rpt, bool nodes_lds,
   }
 #undef LX_MODE
 #undef LX
+#undef LX1
 }
 
 void launch_explain_extended(RowDtype dt, const void* X, const void* nodes,
                              const int32_t* hidx, const float* hw,
                              const float* dl, const float* dr, float* out,
-                             int64_t N, int32_t d, int32_t T,
-                             int32_t max_nodes, int32_t nnz, float fT,
-                             int finalize, int blocks, hipStream_t stream) {
+                             int64_t N, int32_t d, int64_t rs, int64_t cs,
+                             int32_t T, int32_t max_nodes, int32_t nnz,
+                             float fT, int finalize, int blocks,
+                             hipStream_t stream) {
   if (dt == ROW_BF16)
     hipLaunchKernelGGL((explain_extended_kernel<uint16_t>), dim3(blocks),
                        dim3(256), 0, stream, (const uint16_t*)X,
-                       (const int2*)nodes, hidx, hw, dl, dr, out, N, d, T,
-                       max_nodes, nnz, fT, finalize);
+                       (const int2*)nodes, hidx, hw, dl, dr, out, N, d, rs, cs,
+                       T, max_nodes, nnz, fT, finalize);
   else if (dt == ROW_F16)
     hipLaunchKernelGGL((explain_extended_kernel<f16_t>), dim3(blocks),
                        dim3(256), 0, stream, (const f16_t*)X,
-                       (const int2*)nodes, hidx, hw, dl, dr, out, N, d, T,
-                       max_nodes, nnz, fT, finalize);
+                       (const int2*)nodes, hidx, hw, dl, dr, out, N, d, rs, cs,
+                       T, max_nodes, nnz, fT, finalize);
   else
     hipLaunchKernelGGL((explain_extended_kernel<float>), dim3(blocks),
                        dim3(256), 0, stream, (const float*)X,
-                       (const int2*)nodes, hidx, hw, dl, dr, out, N, d, T,
-                       max_nodes, nnz, fT, finalize);
+                       (const int2*)nodes, hidx, hw, dl, dr, out, N, d, rs, cs,
+                       T, max_nodes, nnz, fT, finalize);
 }
 
 }  // namespace ifa

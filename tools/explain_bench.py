@@ -4,6 +4,12 @@ same resident matrix in one process.
 
 Usage: python tools/explain_bench.py [--rows 5000000] [--features 32]
        [--trees 1000] [--dtype bf16] [--reps 5] [--warmup 2] [--extended]
+       [--layout row|pitched|feature] [--copy-first]
+
+--layout and --copy-first are those of tools/score_bench.py: the matrix as
+packed rows, as the first d columns of a matrix 8 columns wider, or as a
+[d, N] buffer seen through .T; --copy-first times .contiguous() plus the
+call, not the call on the view.
 
 Both calls are warmed up, every repetition is bracketed by device
 synchronises, the two calls alternate (same process, same matrix, same
@@ -40,6 +46,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--extended", action="store_true")
     ap.add_argument("--extension-level", type=int, default=None)
+    ap.add_argument("--layout", choices=["row", "pitched", "feature"],
+                    default="row")
+    ap.add_argument("--copy-first", action="store_true")
     args = ap.parse_args()
 
     from isolation_forest_amd import ExtendedIsolationForest, IsolationForest
@@ -55,6 +64,13 @@ def main():
              "fp32": torch.float32}[args.dtype]
     X = torch.randn((args.rows, args.features), device=dev,
                     generator=g).to(dtype)
+    if args.layout == "pitched":
+        wide = torch.empty((args.rows, args.features + 8), device=dev,
+                           dtype=dtype)
+        wide[:, :args.features] = X
+        X = wide[:, :args.features]
+    elif args.layout == "feature":
+        X = X.T.contiguous().T
 
     cls = ExtendedIsolationForest if args.extended else IsolationForest
     kw = {}
@@ -63,14 +79,23 @@ def main():
     model = cls(numEstimators=args.trees, maxSamples=float(args.max_samples),
                 randomSeed=3, **kw).fit(X)
 
+    def rows(x):
+        return x.contiguous() if args.copy_first else x
+
+    def explain(x):
+        return model.feature_contributions(rows(x))
+
+    def score(x):
+        return model.score(rows(x))
+
     for _ in range(args.warmup):
-        model.feature_contributions(X)
-        model.score(X)
+        explain(X)
+        score(X)
     t_explain, t_score = [], []
     for _ in range(args.reps):
-        dt, contrib = timed(model.feature_contributions, X)
+        dt, contrib = timed(explain, X)
         t_explain.append(dt)
-        dt, scores = timed(model.score, X)
+        dt, scores = timed(score, X)
         t_score.append(dt)
     te = statistics.median(t_explain)
     ts = statistics.median(t_score)
@@ -79,6 +104,7 @@ def main():
         "ext_level": args.extension_level if args.extended else None,
         "rows": args.rows, "features": args.features, "trees": args.trees,
         "max_samples": args.max_samples, "dtype": args.dtype,
+        "layout": args.layout, "copy_first": args.copy_first,
         "reps": args.reps, "warmup": args.warmup,
         "explain_ms_median": round(te * 1e3, 3),
         "explain_ms_all": [round(t * 1e3, 3) for t in t_explain],

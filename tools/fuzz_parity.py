@@ -2,7 +2,8 @@
 """Differential GPU<->CPU fuzzer.
 
 Random configurations of (rows, features, subsampling, tree count,
-extension level, row dtype f32/bf16/fp16, bootstrap, data pathologies):
+extension level, row dtype f32/bf16/fp16, row layout packed/pitched/
+feature-major, bootstrap, data pathologies):
 build on the GPU and on the CPU oracle (which sees the upcast matrix), demand BITWISE forest equality; score on both, demand
 the routing contract (bitwise for standard/sparse walks, knife-edge
 tolerance for reassociated dense dots). Exits non-zero on the first
@@ -62,6 +63,10 @@ def one_case(rs: np.random.RandomState, it: int) -> str:
     rowdt = ("f32", "bf16", "f16")[int(rs.randint(0, 3))]
     bf16 = rowdt == "bf16"
     half = rowdt != "f32"  # 2-byte rows: bf16 or fp16
+    # drawn from a stream of its own (keyed by the case's seed), so the
+    # configurations of every --seed are the ones they were before layouts
+    layout = ("row", "pitched", "feature")[
+        int(np.random.RandomState(seed).randint(0, 3))]
     bootstrap = bool(rs.randint(0, 2))
     patho = rs.choice(["normal", "const_col", "dups", "big", "tiny"])
 
@@ -78,12 +83,27 @@ def one_case(rs: np.random.RandomState, it: int) -> str:
         # fp16: mostly subnormals (|x| < 2^-14), multiples of 2^-24
         X *= 1e-5 if rowdt == "f16" else 1e-20
     desc = (f"it={it} rows={rows} d={d} n={n} k={k} T={T} seed={seed} "
-            f"ext={extended} dtype={rowdt} boot={bootstrap} patho={patho}")
+            f"ext={extended} dtype={rowdt} layout={layout} boot={bootstrap} "
+            f"patho={patho}")
 
     Xt = torch.from_numpy(X).to("cuda")
     if half:
         Xt = Xt.to(torch.bfloat16 if bf16 else torch.float16)
         X = Xt.float().cpu().numpy()  # exact upcast: what the kernels see
+    # the same values behind other strides, over a NaN-filled buffer (a read
+    # outside the view would change a walk); consumed in place
+    if layout == "pitched":
+        wide = torch.full((rows + 2, d + 7), float("nan"), dtype=Xt.dtype,
+                          device="cuda")
+        wide[1:rows + 1, 3:3 + d] = Xt
+        Xt = wide[1:rows + 1, 3:3 + d]
+    elif layout == "feature":
+        tall = torch.full((d + 2, rows + 5), float("nan"), dtype=Xt.dtype,
+                          device="cuda")
+        tall[1:d + 1, 2:rows + 2] = Xt.T
+        Xt = tall[1:d + 1, 2:rows + 2].T
+    assert gpu_engine._row_layout(Xt) == (
+        "feature" if layout == "feature" and d > 1 else "row")
 
     bag = cpu_engine.sample_bags(rows, T, n, seed=seed, bootstrap=bootstrap)
     fs = cpu_engine.feature_subsets(d, k, T, seed=seed)

@@ -51,7 +51,7 @@ void launch_v4_level_order(const void* nodes, const int32_t* ncount,
 void launch_score_forest(RowDtype dt, int rpt, bool rows_lds, bool nodes_lds,
                          int ilp, const void* X, const void* nodes,
                          const int32_t* ncount, float* out, int64_t N,
-                         int32_t d, int32_t Tpad,
+                         int32_t d, int64_t rs, int64_t cs, int32_t Tpad,
                          int32_t max_nodes, int32_t height_limit, float fT,
                          float c_norm, int finalize, size_t lds, int blocks,
                          hipStream_t stream);
@@ -59,6 +59,7 @@ void launch_score_extended_dense_v2(RowDtype dt, int D, const void* X,
                                     const void* nodes, const float* values,
                                     const float* hw, const int32_t* ncount,
                                     float* out, int64_t N, int32_t d,
+                                    int64_t rs, int64_t cs,
                                     int32_t T, int32_t max_nodes,
                                     int32_t height_limit, float fT,
                                     float c_norm, int finalize, size_t lds,
@@ -67,7 +68,8 @@ void launch_score_extended_sparse_v2(RowDtype dt, int nnz, const void* X,
                                      const void* nodes, const float* values,
                                      const int32_t* hidx, const float* hw,
                                      const int32_t* ncount, float* out,
-                                     int64_t N, int32_t d, int32_t dpad,
+                                     int64_t N, int32_t d, int64_t rs,
+                                     int64_t cs, int32_t dpad,
                                      int32_t T, int32_t max_nodes,
                                      int32_t height_limit, float fT,
                                      float c_norm, int finalize, size_t lds,
@@ -690,7 +692,7 @@ int main(int argc, char** argv) {
         (N + rows_per_block - 1) / rows_per_block, 8192);
     ifa::launch_score_forest(dt, rpt, rows_lds, nodes_lds, 4, dX, dNodes,
                              (const int32_t*)dNcount, (float*)dOut, N, d,
-                             p.Tpad, p.mn, p.max_depth,
+                             (int64_t)d, (int64_t)1, p.Tpad, p.mn, p.max_depth,
                              (float)p.T, c_norm, 1, lds, blocks, 0);
   } else {
     // routing mirror of ops/gpu_engine.score_extended_forest (the wide-d
@@ -729,8 +731,9 @@ int main(int argc, char** argv) {
         ifa::launch_score_extended_sparse_v2(
             dt, p.nnz, dX, dNodes, (const float*)dVals,
             (const int32_t*)dHidx, (const float*)dHw,
-            (const int32_t*)dNcount, (float*)dOut, N, d, (int32_t)dpad_s,
-            p.T, p.mn, p.max_depth, (float)p.T, c_norm, 1, lds, blocks, 0);
+            (const int32_t*)dNcount, (float*)dOut, N, d, (int64_t)d,
+            (int64_t)1, (int32_t)dpad_s, p.T, p.mn, p.max_depth, (float)p.T,
+            c_norm, 1, lds, blocks, 0);
         goto launched;
       }
       try_sparse = false;
@@ -767,8 +770,9 @@ int main(int argc, char** argv) {
                           hipMemcpyHostToDevice));
       ifa::launch_score_extended_dense_v2(
           dt, D, dX, dNodes, (const float*)dVals, (const float*)dHw,
-          (const int32_t*)dNcount, (float*)dOut, N, d, p.T, p.mn,
-          p.max_depth, (float)p.T, c_norm, 1, lds, blocks, 0);
+          (const int32_t*)dNcount, (float*)dOut, N, d, (int64_t)d,
+          (int64_t)1, p.T, p.mn, p.max_depth, (float)p.T, c_norm, 1, lds,
+          blocks, 0);
     }
   }
 launched:
