@@ -876,3 +876,221 @@ def feature_contributions_extended(fr: ExtendedForest, X: np.ndarray,
             active2[rows] = feat[nxt] >= 0
             active = active2
     return _finalize_contributions(acc, fr.num_trees, finalize)
+
+
+# ---------------------------------------------------------------------------
+# Exact TreeSHAP for standard forests (path-dependent, leaf-path form). No
+# analogue in the reference; the contract is docs/DESIGN.md §9. These
+# functions are the oracle for shap_forest_kernel (bitwise).
+# ---------------------------------------------------------------------------
+
+SHAP_MAX_PATH_FEATURES = 16  # the kernel's c[] holds 17 doubles
+
+
+def shap_weights(max_m: int = SHAP_MAX_PATH_FEATURES) -> np.ndarray:
+    """w[m][k] = k! (m-1-k)! / m!, float64 [max_m + 1, max_m] (row 0 and
+    the cells k >= m are 0): the Shapley weight of a coalition of k of the
+    other m - 1 path features. The kernel's table is the default [17, 16];
+    each cell is the correctly rounded quotient of two exact integers."""
+    w = np.zeros((max_m + 1, max_m), dtype=np.float64)
+    for m in range(1, max_m + 1):
+        for k in range(m):
+            w[m, k] = (math.factorial(k) * math.factorial(m - 1 - k)
+                       / math.factorial(m))
+    return w
+
+
+def shap_tables(forest: Forest):
+    """Cached leaf-path tables of a standard forest, float64,
+    shared by shap_values and the GPU pack. Flat arrays, leaves in (tree,
+    ascending node id) order, entries in order of first appearance on the
+    root-to-leaf path, path nodes in path order within their entry:
+
+    ``tree_leaf_off`` [T+1], ``leaf_L`` f64, ``leaf_node``, ``leaf_ent_off``
+    [leaves+1], ``ent_feat`` int32, ``ent_z`` f64, ``ent_pn_off``
+    [entries+1], ``pn_tree``/``pn_node`` (the internal nodes an entry
+    merges) and ``pn_left`` (True: the path turns left there), plus
+    ``max_m`` and ``root_sum`` = sum_t E[root_t] (float64).
+
+    Dropped by forest.invalidate_derived(), like explain_tables."""
+    tabs = getattr(forest, "_shap_tables", None)
+    if tabs is not None:
+        return tabs
+    if isinstance(forest, ExtendedForest):
+        raise ValueError("SHAP values are defined for standard forests only")
+    E, n = node_expectations(forest)
+    Lall = _leaf_path_values(forest).astype(np.float64)
+    feat_all, right_all = forest.feature, forest.right
+    T = forest.num_trees
+    tree_leaf_off = [0]
+    leaf_L, leaf_node, leaf_ent_off = [], [], [0]
+    ent_feat, ent_z, ent_pn_off = [], [], [0]
+    pn_tree, pn_node, pn_left = [], [], []
+    for t in range(T):
+        feat = feat_all[t].tolist()
+        right = right_all[t].tolist()
+        nt = n[t].tolist()
+        # depth-first walk. In a pre-order layout (right[v] past the whole
+        # left subtree: every forest built here) it meets the leaves in id
+        # order; the sort below makes the order the contract's for any
+        # layout with left = id + 1.
+        found = []  # (leaf id, merged entries)
+        path = []  # (node, went_left)
+        stack = [(0, 0)]  # (node, path length on arrival)
+        while stack:
+            v, plen = stack.pop()
+            del path[plen:]
+            f = feat[v]
+            if f >= 0:
+                stack.append((right[v], plen + 1))
+                stack.append((v + 1, plen + 1))
+                path.append([v, True])
+                continue
+            if f != Forest.LEAF:
+                continue  # pad (never reached from a well-formed root)
+            # `path` holds the ancestors; the turn taken at each is known
+            # from the next node on the path (left child = id + 1)
+            nodes = [pv for pv, _ in path]
+            nxt = nodes[1:] + [v]
+            slot = {}
+            groups = []
+            for pv, child in zip(nodes, nxt):
+                fv = feat[pv]
+                ratio = (float(nt[child]) / float(nt[pv])) if nt[pv] > 0 \
+                    else 0.5
+                k = slot.get(fv)
+                if k is None:
+                    slot[fv] = len(groups)
+                    groups.append([fv, ratio, [(pv, child == pv + 1)]])
+                else:
+                    g = groups[k]
+                    g[1] = g[1] * ratio
+                    g[2].append((pv, child == pv + 1))
+            found.append((v, groups))
+        found.sort(key=lambda leaf: leaf[0])
+        for v, groups in found:
+            leaf_L.append(Lall[t, v])
+            leaf_node.append(v)
+            for fv, z, pns in groups:
+                ent_feat.append(fv)
+                ent_z.append(z)
+                for pv, left in pns:
+                    pn_tree.append(t)
+                    pn_node.append(pv)
+                    pn_left.append(left)
+                ent_pn_off.append(len(pn_node))
+            leaf_ent_off.append(len(ent_feat))
+        tree_leaf_off.append(len(leaf_L))
+    leaf_ent_off = np.asarray(leaf_ent_off, dtype=np.int64)
+    leaf_m = np.diff(leaf_ent_off)
+    tabs = {
+        "tree_leaf_off": np.asarray(tree_leaf_off, dtype=np.int64),
+        "leaf_L": np.asarray(leaf_L, dtype=np.float64),
+        "leaf_node": np.asarray(leaf_node, dtype=np.int64),
+        "leaf_ent_off": leaf_ent_off,
+        "leaf_m": leaf_m,
+        "ent_feat": np.asarray(ent_feat, dtype=np.int32),
+        "ent_z": np.asarray(ent_z, dtype=np.float64),
+        "ent_pn_off": np.asarray(ent_pn_off, dtype=np.int64),
+        "pn_tree": np.asarray(pn_tree, dtype=np.int64),
+        "pn_node": np.asarray(pn_node, dtype=np.int64),
+        "pn_left": np.asarray(pn_left, dtype=bool),
+        "max_m": int(leaf_m.max(initial=0)),
+        "root_sum": float(E[:, 0].sum()) if T else 0.0,
+    }
+    forest._shap_tables = tabs
+    return tabs
+
+
+def _shap_leaf_terms(o: np.ndarray, z: np.ndarray, L: np.ndarray,
+                     w: np.ndarray) -> np.ndarray:
+    """The §9 inner loop for G leaves that all merge m features: o bool
+    [N, G, m], z f64 [G, m], L f64 [G] -> the terms (L*(o_a - z_a))*W,
+    f64 [N, G, m]. Every operation is one separately rounded float64
+    numpy ufunc, in the contract's order."""
+    N, G, m = o.shape
+    out = np.empty((N, G, m), dtype=np.float64)
+    of = o.astype(np.float64)
+    for a in range(m):
+        c = np.zeros((m + 1, N, G), dtype=np.float64)
+        c[0] = 1.0
+        cnt = 0
+        for b in range(m):
+            if b == a:
+                continue
+            ob = o[:, :, b]
+            zb = z[None, :, b]
+            for k in range(cnt, -1, -1):
+                c[k + 1] = np.where(ob, c[k + 1] + c[k], c[k + 1])
+                c[k] = c[k] * zb
+            cnt += 1
+        W = np.zeros((N, G), dtype=np.float64)
+        for k in range(m):
+            W = W + c[k] * w[m][k]
+        out[:, :, a] = (L[None, :] * (of[:, :, a] - z[None, :, a])) * W
+    return out
+
+
+def shap_raw_sums(forest: Forest, X: np.ndarray) -> np.ndarray:
+    """float64 [N, d]: the unrounded accumulators of shap_values (the sums
+    over trees, before the division by T and the float32 rounding)."""
+    X = np.asarray(X)
+    N, d = X.shape
+    tabs = shap_tables(forest)
+    fmax = int(tabs["ent_feat"].max(initial=-1))
+    if fmax >= d:
+        raise ValueError(
+            f"the forest splits on feature {fmax} but rows have {d} columns")
+    w = shap_weights(max(tabs["max_m"], SHAP_MAX_PATH_FEATURES))
+    v64_all = (forest.value64 if getattr(forest, "value64", None) is not None
+               else forest.value.astype(np.float64))
+    X64 = X.astype(np.float64)
+    acc = np.zeros((N, d), dtype=np.float64)
+    leaf_ent_off, leaf_m = tabs["leaf_ent_off"], tabs["leaf_m"]
+    ent_feat, ent_z = tabs["ent_feat"], tabs["ent_z"]
+    ent_pn_off = tabs["ent_pn_off"]
+    n_leaves = len(tabs["leaf_L"])
+    # leaves in chunks that bound the [N, entries] temporaries
+    chunk = max(1, int(4e6 // max(N * max(tabs["max_m"], 1), 1)))
+    for l0 in range(0, n_leaves, chunk):
+        l1 = min(n_leaves, l0 + chunk)
+        e0, e1 = int(leaf_ent_off[l0]), int(leaf_ent_off[l1])
+        if e1 == e0:
+            continue  # single-leaf trees carry no entry
+        p0, p1 = int(ent_pn_off[e0]), int(ent_pn_off[e1])
+        pt, pv = tabs["pn_tree"][p0:p1], tabs["pn_node"][p0:p1]
+        # the engine's own decision: f64(x) < value64, NaN goes right
+        goes_left = X64[:, forest.feature[pt, pv]] < v64_all[pt, pv][None, :]
+        agree = goes_left == tabs["pn_left"][p0:p1][None, :]
+        o_ent = np.logical_and.reduceat(agree, ent_pn_off[e0:e1] - p0, axis=1)
+        terms = np.empty((N, e1 - e0), dtype=np.float64)
+        ms = leaf_m[l0:l1]
+        for m in np.unique(ms):
+            if m == 0:
+                continue
+            ls = np.nonzero(ms == m)[0] + l0
+            cols = (leaf_ent_off[ls][:, None] - e0
+                    + np.arange(m, dtype=np.int64)[None, :])  # [G, m]
+            tm = _shap_leaf_terms(o_ent[:, cols], ent_z[cols + e0],
+                                  tabs["leaf_L"][ls], w)
+            terms[:, cols.reshape(-1)] = tm.reshape(N, -1)
+        # the adds, in the contract's order: tree, leaf, entry
+        for e in range(e0, e1):
+            f = ent_feat[e]
+            acc[:, f] = acc[:, f] + terms[:, e - e0]
+    return acc
+
+
+def shap_values(forest: Forest, X: np.ndarray,
+                finalize: bool = True) -> np.ndarray:
+    """Exact path-dependent TreeSHAP values, float32 [N, d]:
+    the Shapley values of the game sum_t v_t(S), where v_t descends tree t
+    taking the row's branch at splits on features in S and the
+    cover-weighted average of both children elsewhere. finalize=True
+    returns f32(acc / f64(T)), else f32(acc); with expected_path_length
+    the row sums reproduce the mean path length. Negative = more
+    anomalous, as in feature_contributions."""
+    acc = shap_raw_sums(forest, X)
+    if finalize:
+        acc = acc / np.float64(forest.num_trees)
+    return acc.astype(np.float32)

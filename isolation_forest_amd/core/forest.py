@@ -97,11 +97,12 @@ class Forest:
 
     def invalidate_derived(self):
         """Drop tables derived from the arrays (the attribution tables of
-        cpu_engine.explain_tables). A forest is treated as immutable once
-        it has been scored or explained: those caches, like a model's
-        device packs, are not keyed on the arrays' contents, so code that
-        edits the arrays in place afterwards must call this."""
+        cpu_engine.explain_tables and shap_tables). A forest is treated as
+        immutable once it has been scored or explained: those caches, like
+        a model's device packs, are not keyed on the arrays' contents, so
+        code that edits the arrays in place afterwards must call this."""
         self.__dict__.pop("_explain_tables", None)
+        self.__dict__.pop("_shap_tables", None)
 
     def leaf_values_from_counts(self):
         """(Re)compute leaf path-length terms from num_instances in place."""
@@ -185,6 +186,7 @@ class ExtendedForest:
     def invalidate_derived(self):
         """See Forest.invalidate_derived."""
         self.__dict__.pop("_explain_tables", None)
+        self.__dict__.pop("_shap_tables", None)
 
     def leaf_values_from_counts(self):
         self.invalidate_derived()

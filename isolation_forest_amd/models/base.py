@@ -133,14 +133,28 @@ class ModelBase:
     _explain_cpu = None  # cpu_engine function (forest, X, finalize)
     _explain_gpu = None  # gpu_engine function name (model, X, finalize)
 
-    def feature_contributions(self, X, finalize: bool = True) -> torch.Tensor:
+    EXPLAIN_METHODS = ("path", "shap")
+
+    def feature_contributions(self, X, finalize: bool = True,
+                              method: str = "path") -> torch.Tensor:
         """Per-feature path-length contributions, float32 [N, d] on X's
         device. ``expected_path_length + contributions[i].sum()`` is row
         i's mean path length; a NEGATIVE entry means the feature shortened
         the path, i.e. made the row more anomalous. ``finalize=False``
-        returns the raw per-tree sums (not divided by the tree count)."""
+        returns the raw per-tree sums (not divided by the tree count).
+
+        ``method="path"`` (default) credits the splits on the row's own
+        root-to-leaf paths. ``method="shap"`` returns exact
+        path-dependent TreeSHAP values (standard forests
+        only): same bias, same sign convention, same row sums."""
+        if method not in self.EXPLAIN_METHODS:
+            raise ValueError(
+                f"unknown attribution method {method!r}: expected one of "
+                f"{self.EXPLAIN_METHODS}")
         self._check_scorable()
         validate_feature_vector_size(self.forest.total_num_features, X.shape[1])
+        if method == "shap":
+            return self._shap_values(X, finalize)
         if isinstance(X, torch.Tensor) and X.is_cuda:
             from ..ops import gpu_engine
 
@@ -148,6 +162,29 @@ class ModelBase:
         Xc = X.contiguous().float().numpy() if isinstance(X, torch.Tensor) else X
         return torch.from_numpy(
             type(self)._explain_cpu(self.forest, Xc, finalize))
+
+    def _shap_values(self, X, finalize: bool) -> torch.Tensor:
+        from ..core import cpu_engine
+        from ..core.forest import ExtendedForest
+
+        if isinstance(self.forest, ExtendedForest):
+            raise ValueError(
+                'method="shap" is not available for extended models: one '
+                "hyperplane node involves several features, so the "
+                "path-dependent value function (follow the row where the "
+                "split feature is known, average the children elsewhere) is "
+                "not defined for it")
+        if isinstance(X, torch.Tensor) and X.is_cuda:
+            from ..ops import gpu_engine
+
+            return gpu_engine.shap_forest(self, X, finalize)
+        Xc = X.contiguous().float().numpy() if isinstance(X, torch.Tensor) else X
+        return torch.from_numpy(
+            cpu_engine.shap_values(self.forest, Xc, finalize))
+
+    def shap_values(self, X, finalize: bool = True) -> torch.Tensor:
+        """Alias of ``feature_contributions(X, finalize, method="shap")``."""
+        return self.feature_contributions(X, finalize, method="shap")
 
     @property
     def expected_path_length(self) -> float:
@@ -161,13 +198,14 @@ class ModelBase:
                 cpu_engine.expected_path_length(self.forest))
         return self._expected_path_length
 
-    def top_contributing_features(self, X, k: int):
+    def top_contributing_features(self, X, k: int, method: str = "path"):
         """(indices int64 [N, k], values float32 [N, k]): the k most
-        negative contributions per row, most negative first."""
+        negative contributions per row, most negative first. ``method`` as
+        in feature_contributions."""
         d = int(X.shape[1])
         if not 1 <= int(k) <= d:
             raise ValueError(f"k must be in [1, {d}], got {k}")
-        contrib = self.feature_contributions(X)
+        contrib = self.feature_contributions(X, method=method)
         values, indices = torch.topk(contrib, int(k), dim=1, largest=False,
                                      sorted=True)
         return indices, values

@@ -498,6 +498,62 @@ def _nodes_packed_explain(forest, d_sentinel: int, bf16):
     return packed, max(max_depth, 1)
 
 
+def _shap_packed(forest, kind):
+    """Leaf-path word stream for shap_forest_kernel (layout in
+    ops/hip/shap_kernels.hip) from cpu_engine.shap_tables, for one row kind:
+    per leaf {f64 L, m}, then m entries {f64 z, lo | hi << 32, feature}.
+
+    [lo, hi] is the INCLUSIVE interval of widened row keys that take the
+    path's branch at every node the entry merges. A row goes left iff
+    widen(key(x)) < threshold key (_nodes_packed_v4's thresholds), so lo is
+    the max threshold over the right turns (0: none) and hi the min over
+    the left turns, minus 1 (0xFFFFFFFF: none; the NaN key passes, NaN goes
+    right). A left turn at threshold key 0 is never taken: the entry gets
+    the empty interval lo = 1, hi = 0 rather than a wrapped hi.
+    Returns (words uint64 [W], tree_off int64 [T + 1] in words)."""
+    from ..core.cpu_engine import shap_tables
+
+    tabs = shap_tables(forest)
+    T = forest.num_trees
+    thr = np.zeros(forest.feature.shape, dtype=np.uint32)
+    internal = forest.feature >= 0
+    if internal.any():
+        s = _split_thresholds32(forest)[internal]
+        thr[internal] = _threshold_keys(s, kind)
+    ent_off = tabs["leaf_ent_off"]
+    n_ent = len(tabs["ent_feat"])
+    pn_ent = np.repeat(np.arange(n_ent, dtype=np.int64),
+                       np.diff(tabs["ent_pn_off"]))
+    pn_key = thr[tabs["pn_tree"], tabs["pn_node"]].astype(np.int64)
+    left = tabs["pn_left"]
+    lo = np.zeros(n_ent, dtype=np.int64)
+    hi = np.full(n_ent, 1 << 32, dtype=np.int64)  # exclusive, none yet
+    np.maximum.at(lo, pn_ent[~left], pn_key[~left])
+    np.minimum.at(hi, pn_ent[left], pn_key[left])
+    never = hi == 0
+    lo[never] = 1
+    hi = np.where(never, 0, hi - 1)  # inclusive
+
+    leaf_m = tabs["leaf_m"]
+    n_leaf = len(leaf_m)
+    leaf_word = 2 * np.arange(n_leaf, dtype=np.int64) + 3 * ent_off[:-1]
+    total = 2 * n_leaf + 3 * n_ent
+    words = np.zeros(total, dtype=np.uint64)
+    words[leaf_word] = tabs["leaf_L"].view(np.uint64)
+    words[leaf_word + 1] = leaf_m.astype(np.uint64)
+    ent_leaf = np.repeat(np.arange(n_leaf, dtype=np.int64), leaf_m)
+    ent_word = (leaf_word[ent_leaf] + 2
+                + 3 * (np.arange(n_ent, dtype=np.int64) - ent_off[ent_leaf]))
+    words[ent_word] = tabs["ent_z"].view(np.uint64)
+    words[ent_word + 1] = (lo.astype(np.uint64)
+                           | (hi.astype(np.uint64) << np.uint64(32)))
+    words[ent_word + 2] = tabs["ent_feat"].astype(np.uint64)
+    tlo = tabs["tree_leaf_off"]
+    tree_off = (2 * tlo + 3 * ent_off[tlo]).astype(np.int64)
+    assert tree_off[0] == 0 and tree_off[T] == total
+    return words, np.ascontiguousarray(tree_off)
+
+
 def _eif_packed_wide(forest):
     """Wide int4 node records {is_leaf(-1)/0, right, value_bits, 0} for
     score_extended_wide (strict oracle j-order dot from global
@@ -899,9 +955,10 @@ def _device_forest(model, device, v4_key=None):
     """Cached device copy of the packed forest. v4_key = (d, kind) selects
     the standard-scoring v4 packing; None = the EIF packing. Packs that
     hold integer key thresholds — (d, kind), ("wide", kind),
-    ("eif0", d, kind), ("explain", d, kind) — are keyed on the row KIND, not
-    on "is it 16-bit": bf16 and fp16 keys differ, and u32 records under a
-    u16 kernel score silently wrong."""
+    ("eif0", d, kind), ("explain", d, kind), ("shap", d, kind) — are keyed
+    on the row KIND, not on "is it 16-bit": bf16 and fp16 keys differ, and
+    u32 records under a u16 kernel score silently wrong. The "shap" entry
+    is (table words, per-tree word offsets, {host offsets, weights})."""
     if isinstance(v4_key, tuple) and v4_key[0] not in ("eif_dense",
                                                        "eif_dense3"):
         v4_key = v4_key[:-1] + (_row_kind(v4_key[-1]),)
@@ -997,6 +1054,14 @@ def _device_forest(model, device, v4_key=None):
                 np.ascontiguousarray(forest.node_count, dtype=np.int32)
             ).to(device)
             extra["height"] = max_depth
+        elif isinstance(v4_key, tuple) and v4_key[0] == "shap":
+            from ..core.cpu_engine import shap_weights
+
+            words, tree_off = _shap_packed(forest, v4_key[2])
+            aos = torch.from_numpy(words.view(np.int64)).to(device)
+            ncount = torch.from_numpy(tree_off).to(device)  # word offsets
+            extra["tree_off_host"] = torch.from_numpy(tree_off)
+            extra["wtab"] = torch.from_numpy(shap_weights()).to(device)
         elif v4_key == "eif_explain":
             from ..core.cpu_engine import explain_tables
 
@@ -1272,3 +1337,52 @@ def explain_extended_forest(model, X: torch.Tensor,
     return ext.explain_extended_forest(
         _rows_in_place(X), aos, extra["hidx"], extra["hw"], extra["dl"],
         extra["dr"], finalize)
+
+
+# ---------------------------------------------------------------------------
+# exact TreeSHAP, standard forests (docs/DESIGN.md §9)
+# ---------------------------------------------------------------------------
+
+
+def _shap_on_cpu(forest, X: torch.Tensor, finalize: bool, why: str):
+    """CPU oracle, result moved to X's device (a correctness path)."""
+    from ..core import cpu_engine
+
+    _log.warning("shap_values: %s; computing on the CPU oracle", why)
+    Xc = X.detach().float().cpu().contiguous().numpy()
+    return torch.from_numpy(
+        cpu_engine.shap_values(forest, Xc, finalize)).to(X.device)
+
+
+def shap_forest(model, X: torch.Tensor, finalize: bool = True) -> torch.Tensor:
+    """Standard-forest SHAP values [N, d] float32 on X's device, bitwise
+    equal to cpu_engine.shap_values."""
+    from ..core import cpu_engine
+
+    forest = model.forest
+    if isinstance(forest, ExtendedForest):
+        raise ValueError("SHAP values are defined for standard forests only")
+    d = int(X.shape[1])
+    if X.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError("shap_values expects float32, bfloat16 or float16 "
+                         f"rows on the GPU, got {X.dtype}")
+    fmax = int(forest.feature.max(initial=-1))
+    if fmax >= d:
+        raise ValueError(
+            f"the forest splits on feature {fmax} but rows have {d} columns")
+    if not _packed_fits(forest, d):
+        return _shap_on_cpu(
+            forest, X, finalize,
+            "forest exceeds the packed node format (15-bit node ids, "
+            "12-bit feature ids)")
+    max_m = cpu_engine.shap_tables(forest)["max_m"]
+    if max_m > cpu_engine.SHAP_MAX_PATH_FEATURES:
+        return _shap_on_cpu(
+            forest, X, finalize,
+            f"a root-to-leaf path splits on {max_m} distinct features, the "
+            f"kernel holds {cpu_engine.SHAP_MAX_PATH_FEATURES}")
+    ext = load_extension()
+    table, tree_off, extra = _device_forest(
+        model, X.device, v4_key=("shap", d, _row_kind(X.dtype)))
+    return ext.shap_forest(_rows_in_place(X), table, extra["tree_off_host"],
+                           tree_off, extra["wtab"], finalize)

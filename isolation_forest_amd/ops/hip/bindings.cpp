@@ -138,6 +138,15 @@ void launch_explain_extended(RowDtype dt, const void* X, const void* nodes,
                              float fT, int finalize, int blocks,
                              hipStream_t stream);
 
+// shap_kernels.hip
+void launch_shap_forest(RowDtype dt, bool table_lds, bool acc_lds,
+                        const void* X, const void* table,
+                        const int64_t* tree_off, const double* wtab,
+                        double* acc_g, float* out, int64_t N, int32_t d,
+                        int64_t rs, int64_t cs, int32_t T, int32_t table_words,
+                        int rows_lds, int finalize, size_t lds, int blocks,
+                        hipStream_t stream);
+
 }  // namespace ifa
 
 namespace {
@@ -849,6 +858,96 @@ torch::Tensor explain_extended_forest(torch::Tensor X,
   return out;
 }
 
+// Exact TreeSHAP, standard forests (shap_forest_kernel, docs/DESIGN.md §9).
+// `table` is the leaf-path word stream of gpu_engine._shap_packed for X's row
+// kind, `tree_off` its per-tree word offsets: once on the host (checked
+// here, it sizes the LDS staging) and once on the device (read by the
+// kernel). Returns the f32 [N, d] SHAP matrix (raw sums when !finalize).
+torch::Tensor shap_forest(torch::Tensor X, torch::Tensor table,
+                          torch::Tensor tree_off_host, torch::Tensor tree_off,
+                          torch::Tensor wtab, bool finalize) {
+  CHECK_CUDA(X);
+  CHECK_CUDA(table);
+  CHECK_CONTIG(table);
+  CHECK_CUDA(tree_off);
+  CHECK_CONTIG(tree_off);
+  CHECK_CUDA(wtab);
+  CHECK_CONTIG(wtab);
+  CHECK_CONTIG(tree_off_host);
+  check_x(X);
+  const XLayout xl = check_x_layout(X);
+  TORCH_CHECK(table.dim() == 1 && table.scalar_type() == torch::kInt64,
+              "table must be the int64 word stream");
+  TORCH_CHECK(!tree_off_host.is_cuda() && tree_off_host.dim() == 1 &&
+                  tree_off_host.scalar_type() == torch::kInt64 &&
+                  tree_off_host.size(0) >= 2,
+              "tree_off_host must be a host int64 [T + 1]");
+  TORCH_CHECK(tree_off.dim() == 1 && tree_off.scalar_type() == torch::kInt64 &&
+                  tree_off.size(0) == tree_off_host.size(0),
+              "tree_off must be int64 [T + 1] like tree_off_host");
+  TORCH_CHECK(wtab.scalar_type() == torch::kFloat64 && wtab.numel() == 17 * 16,
+              "wtab must be float64 [17, 16]");
+  const int64_t N = X.size(0), d = X.size(1);
+  const int64_t T = tree_off_host.size(0) - 1;
+  const int64_t* to = tree_off_host.data_ptr<int64_t>();
+  TORCH_CHECK(to[0] == 0 && to[T] == table.numel(),
+              "tree_off must span the table exactly");
+  int64_t table_words = 0;
+  for (int64_t t = 0; t < T; ++t) {
+    TORCH_CHECK(to[t + 1] >= to[t], "tree_off must be non-decreasing");
+    table_words = std::max(table_words, to[t + 1] - to[t]);
+  }
+  TORCH_CHECK(table_words < (int64_t)1 << 28, "one tree's table is too large");
+  TORCH_CHECK(d >= 1 && d <= 4094, "shap supports 1 <= d <= 4094");
+  const auto out_opts = X.options().dtype(torch::kFloat32);
+  if (N == 0) return torch::empty({N, d}, out_opts);
+
+  const ifa::RowDtype dt = row_dtype(X);
+  const size_t elem = (size_t)ifa::row_elem_bytes(dt);
+  const size_t budget = 150 * 1024;
+  const size_t wtab_b = 17 * 16 * 8;
+  const size_t keys_b = align16((size_t)256 * d * elem);
+  const size_t acc_b = (size_t)256 * d * 8;
+  const size_t table_b = (size_t)table_words * 8;
+  // what goes to LDS, in this order of preference: the key tile, the
+  // accumulators (touched once per term by every lane), one tree's table
+  // (broadcast reads, L2 serves them well)
+  const bool rows_lds = wtab_b + keys_b <= budget;
+  size_t lds = wtab_b + (rows_lds ? keys_b : 0);
+  // The accumulator tile is taken only while two blocks still fit a CU.
+  // Measured (profiles/shap.md): with two or more resident blocks either
+  // way the LDS tile is 3 % faster than the global scratch; a tile that
+  // holds a CU to one block (one wave per SIMD) is 27 % slower than it.
+  const size_t all_lds =
+      lds + acc_b + (lds + acc_b + table_b <= budget ? table_b : 0);
+  bool acc_lds = lds + acc_b <= budget && all_lds <= kMaxLds / 2;
+  if (const char* e = getenv("IFA_SHAP_FORCE_GLOBAL_ACC"))
+    if (atoi(e)) acc_lds = false;
+  if (acc_lds) lds += acc_b;
+  bool table_lds = lds + table_b <= budget;
+  if (const char* e = getenv("IFA_SHAP_FORCE_GLOBAL_TABLE"))
+    if (atoi(e)) table_lds = false;
+  if (table_lds) lds += table_b;
+
+  auto out = torch::empty({N, d}, out_opts);
+  torch::Tensor acc_g;
+  if (!acc_lds)
+    acc_g = torch::zeros({N, d}, X.options().dtype(torch::kFloat64));
+  int64_t max_blocks = 8192;
+  if (const char* e = getenv("IFA_SHAP_MAX_BLOCKS")) {
+    const int64_t v = atoll(e);
+    if (v >= 1) max_blocks = std::min<int64_t>(v, 8192);
+  }
+  const int blocks = (int)std::min<int64_t>((N + 255) / 256, max_blocks);
+  ifa::launch_shap_forest(
+      dt, table_lds, acc_lds, X.data_ptr(), table.data_ptr<int64_t>(),
+      tree_off.data_ptr<int64_t>(), wtab.data_ptr<double>(),
+      acc_lds ? nullptr : acc_g.data_ptr<double>(), out.data_ptr<float>(), N,
+      (int32_t)d, xl.rs, xl.cs, (int32_t)T, (int32_t)table_words,
+      rows_lds ? 1 : 0, finalize ? 1 : 0, lds, blocks, current_stream());
+  return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bag_gather", &bag_gather, "gather per-tree bags (K9/K10)");
   m.def("build_forest", &build_forest, "build standard iTrees (K1/K2/K11)");
@@ -873,5 +972,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-feature path-length attribution, standard forests");
   m.def("explain_extended_forest", &explain_extended_forest,
         "per-feature path-length attribution, extended forests");
+  m.def("shap_forest", &shap_forest,
+        "exact path-dependent TreeSHAP values, standard forests");
   m.attr("WAVE") = 64;
 }

@@ -14,6 +14,7 @@ import torch
 from fastapi import FastAPI, HTTPException
 from pydantic import BaseModel, Field
 
+from ..core.forest import ExtendedForest
 from ..persist import model_io
 
 
@@ -30,6 +31,12 @@ class ScoreRequest(BaseModel):
         ..., description="batch of feature rows, shape [n, numFeatures]")
 
 
+class ExplainRequest(ScoreRequest):
+    # "path" (the default when absent): the row's own root-to-leaf splits;
+    # "shap": exact TreeSHAP values (standard models only)
+    method: Optional[str] = None
+
+
 class ScoreResponse(BaseModel):
     scores: List[float]
     labels: Optional[List[int]] = None  # only when a threshold is set
@@ -41,6 +48,9 @@ class ExplainResponse(BaseModel):
     contributions: List[List[float]]
     expectedPathLength: float
     scores: List[float]
+    # echo of the request's "method"; left out when the request named none,
+    # so the default response is what it always was
+    method: Optional[str] = None
 
 
 def create_app(model_path: str, device: str = None) -> FastAPI:
@@ -108,19 +118,31 @@ def create_app(model_path: str, device: str = None) -> FastAPI:
             labels = (scores_np >= threshold).astype(int).tolist()
         return ScoreResponse(scores=scores_np.tolist(), labels=labels)
 
-    @app.post("/v1/explain", response_model=ExplainResponse)
-    def explain(req: ScoreRequest):
+    @app.post("/v1/explain", response_model=ExplainResponse,
+              response_model_exclude_none=True)
+    def explain(req: ExplainRequest):
         """Per-feature contributions next to the scores (same request shape
-        and validation as /v1/score)."""
+        and validation as /v1/score, plus an optional "method")."""
+        method = "path" if req.method is None else req.method
+        if method not in model.EXPLAIN_METHODS:
+            raise HTTPException(
+                status_code=400,
+                detail=f"unknown method {method!r}: expected one of "
+                       f"{list(model.EXPLAIN_METHODS)}")
+        if method == "shap" and isinstance(model.forest, ExtendedForest):
+            raise HTTPException(
+                status_code=400,
+                detail='method "shap" is not available for extended models '
+                       "(a hyperplane node involves several features)")
         if not req.instances:
             return ExplainResponse(
-                contributions=[], scores=[],
+                contributions=[], scores=[], method=req.method,
                 expectedPathLength=model.expected_path_length)
         X = parse_instances(req)
         try:
             with torch.no_grad():
                 Xt = torch.from_numpy(X).to(dev)
-                contrib = model.feature_contributions(Xt)
+                contrib = model.feature_contributions(Xt, method=method)
                 scores = model.score(Xt)
         except (IndexError, RuntimeError, ValueError) as e:
             raise HTTPException(status_code=400,
@@ -128,6 +150,7 @@ def create_app(model_path: str, device: str = None) -> FastAPI:
         return ExplainResponse(
             contributions=contrib.float().cpu().numpy().tolist(),
             expectedPathLength=model.expected_path_length,
-            scores=scores.float().cpu().numpy().tolist())
+            scores=scores.float().cpu().numpy().tolist(),
+            method=req.method)
 
     return app

@@ -21,6 +21,7 @@ ext = CUDAExtension(
     sources=[
         "isolation_forest_amd/ops/hip/bindings.cpp",
         "isolation_forest_amd/ops/hip/forest_kernels.hip",
+        "isolation_forest_amd/ops/hip/shap_kernels.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],

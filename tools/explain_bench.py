@@ -4,7 +4,12 @@ same resident matrix in one process.
 
 Usage: python tools/explain_bench.py [--rows 5000000] [--features 32]
        [--trees 1000] [--dtype bf16] [--reps 5] [--warmup 2] [--extended]
-       [--layout row|pitched|feature] [--copy-first]
+       [--layout row|pitched|feature] [--copy-first] [--method path|shap]
+
+--method is feature_contributions' own: "path" (default) times the
+path-length decomposition, "shap" the exact TreeSHAP kernel (standard
+forests only; expect orders of magnitude below "path", it visits every
+leaf of every tree).
 
 --layout and --copy-first are those of tools/score_bench.py: the matrix as
 packed rows, as the first d columns of a matrix 8 columns wider, or as a
@@ -49,7 +54,10 @@ def main():
     ap.add_argument("--layout", choices=["row", "pitched", "feature"],
                     default="row")
     ap.add_argument("--copy-first", action="store_true")
+    ap.add_argument("--method", choices=["path", "shap"], default="path")
     args = ap.parse_args()
+    if args.method == "shap" and args.extended:
+        raise SystemExit("--method shap is defined for standard forests only")
 
     from isolation_forest_amd import ExtendedIsolationForest, IsolationForest
     from isolation_forest_amd.ops import load_extension
@@ -83,7 +91,7 @@ def main():
         return x.contiguous() if args.copy_first else x
 
     def explain(x):
-        return model.feature_contributions(rows(x))
+        return model.feature_contributions(rows(x), method=args.method)
 
     def score(x):
         return model.score(rows(x))
@@ -100,7 +108,9 @@ def main():
     te = statistics.median(t_explain)
     ts = statistics.median(t_score)
     print(json.dumps({
-        "kernel": "explain_extended" if args.extended else "explain",
+        "kernel": ("explain_extended" if args.extended
+                   else "shap" if args.method == "shap" else "explain"),
+        "method": args.method,
         "ext_level": args.extension_level if args.extended else None,
         "rows": args.rows, "features": args.features, "trees": args.trees,
         "max_samples": args.max_samples, "dtype": args.dtype,
