@@ -951,6 +951,25 @@ def _v4_walk_order(aos: torch.Tensor, ncount: torch.Tensor) -> torch.Tensor:
                                                ncount.contiguous())
 
 
+def _v4_heap_records(aos: torch.Tensor, ncount: torch.Tensor, d: int, kind,
+                     height: int):
+    """Pre-order v4 records -> the 4-byte heap records score_forest_heap
+    walks (16-bit rows; forest_kernels.hip), or None where the extension's
+    score_route keeps these shapes on the v4 kernels. Packing, like
+    _v4_walk_order; cached with the pack under extra["heap"]."""
+    kind = _row_kind(kind)
+    if kind == "f32":
+        return None
+    from . import load_extension as _packing_extension
+
+    ext = _packing_extension()
+    if ext.score_route(kind, int(d), int(aos.shape[1]), int(height),
+                       "packed") != "heap":
+        return None
+    return ext.v4_heap_order(aos.contiguous(), ncount.contiguous(),
+                             int(height), int(d))
+
+
 def _device_forest(model, device, v4_key=None):
     """Cached device copy of the packed forest. v4_key = (d, kind) selects
     the standard-scoring v4 packing; None = the EIF packing. Packs that
@@ -1044,7 +1063,10 @@ def _device_forest(model, device, v4_key=None):
             packed, ncount_np, max_depth = _eif0_packed_v4(
                 forest, v4_key[1], v4_key[2])
             ncount = torch.from_numpy(ncount_np).to(device)
-            aos = _v4_walk_order(torch.from_numpy(packed).to(device), ncount)
+            aos = torch.from_numpy(packed).to(device)
+            extra["heap"] = _v4_heap_records(aos, ncount, v4_key[1],
+                                             v4_key[2], max(max_depth, 1))
+            aos = _v4_walk_order(aos, ncount)
             extra["height"] = max_depth
         elif isinstance(v4_key, tuple) and v4_key[0] == "explain":
             packed, max_depth = _nodes_packed_explain(
@@ -1102,6 +1124,7 @@ def _device_forest(model, device, v4_key=None):
                 packed, ncount_np, max_depth = _nodes_packed_v4(forest, d, kind)
                 aos = torch.from_numpy(packed).to(device)
                 ncount = torch.from_numpy(ncount_np).to(device)
+            extra["heap"] = _v4_heap_records(aos, ncount, d, kind, max_depth)
             aos = _v4_walk_order(aos, ncount)
             extra["height"] = max_depth
         else:
@@ -1151,7 +1174,7 @@ def score_forest(model, X: torch.Tensor, finalize: bool = True) -> torch.Tensor:
     aos, ncount, extra = _device_forest(model, X.device, v4_key=(d, kind))
     return ext.score_forest(
         _rows_in_place(X), aos, ncount, forest.num_trees, extra["height"], c,
-        finalize,
+        finalize, extra["heap"],
     )
 
 
@@ -1200,7 +1223,7 @@ def score_extended_forest(model, X: torch.Tensor, finalize: bool = True) -> torc
             model, X.device, v4_key=("eif0", d, _row_kind(X.dtype)))
         return ext.score_forest(
             _rows_in_place(X), aos, ncount, forest.num_trees, extra["height"],
-            c, finalize,
+            c, finalize, extra["heap"],
         )
     if nnz <= 5 and _eif_uniform_nnz(forest):
         elem = 4 if X.dtype == torch.float32 else 2  # bf16 / fp16

@@ -7,6 +7,7 @@
 #include <torch/extension.h>
 
 #include <algorithm>
+#include <string>
 #include <vector>
 
 #include "row_dtype.h"
@@ -40,6 +41,18 @@ void launch_build_extended_forest(const float* bags, const int32_t* feat_sub,
 void launch_v4_level_order(const void* nodes, const int32_t* ncount,
                            void* out, int32_t Tpad, int32_t max_nodes,
                            hipStream_t stream);
+
+void launch_v4_heap_order(const void* nodes, const int32_t* ncount,
+                          void* out, int32_t Tpad, int32_t max_nodes,
+                          int32_t height, int32_t slab_bytes,
+                          hipStream_t stream);
+
+void launch_score_forest_heap(RowDtype dt, int rpt, const void* X,
+                              const void* heap, float* out, int64_t N,
+                              int32_t d, int64_t rs, int64_t cs, int32_t Tpad,
+                              int32_t height, float fT, float c_norm,
+                              int finalize, size_t lds, int blocks,
+                              hipStream_t stream);
 
 void launch_score_forest(RowDtype dt, int rpt, bool rows_lds, bool nodes_lds,
                          int ilp, const void* X, const void* nodes,
@@ -207,6 +220,120 @@ XLayout check_x_layout(const torch::Tensor& X) {
   return {1, s1};
 }
 
+// The instantiation one standard scoring call runs, from shapes alone (and
+// the IFA_SCORE_* switches). score_forest launches by it, v4_heap_order lays
+// the heap records out for it, and score_route reports it.
+struct ScoreCfg {
+  // score_forest_v4
+  int rpt, ilp;
+  bool rows_lds, nodes_lds;
+  size_t lds;
+  // score_forest_heap: taken when `heap` and the caller has the records
+  bool heap;
+  int heap_rpt;
+  size_t heap_lds;
+};
+
+ScoreCfg pick_score_cfg(int elem_bytes, int64_t d, int64_t max_nodes,
+                        int64_t height) {
+  ScoreCfg c{};
+  const size_t elem = (size_t)elem_bytes;
+  // staged-tree ILP: 4 (default) or 8; 8 halves the number of barrier-
+  // bounded staging phases at the cost of occupancy (A/B via env)
+  int ilp = 4;
+  bool ilp_forced = false;
+  if (const char* e = getenv("IFA_SCORE_ILP")) {
+    ilp = atoi(e) == 8 ? 8 : 4;
+    ilp_forced = ilp == 8;
+  }
+  // feature-major key tile: d feature slabs plus the sentinel slab, each
+  // rows_per_block keys, lane-adjacent — no padding needed
+  const int64_t slabs = d + 1;
+  // deep forests (large maxSamples) overflow LDS node staging: walk nodes
+  // from global/L2 instead (NODES_LDS=false) — correct for any tree size
+  bool nodes_lds =
+      (size_t)2 * max_nodes * 8 + (size_t)256 * slabs * elem <= 150 * 1024;
+  // config search over (rpt, ilp): wide-d rows inflate the LDS row tile,
+  // so dropping staged-tree ILP to 2 can buy back a resident block
+  // (measured: d=128 went 1 block/CU at ILP=4 -> 124M rows/s; ILP=2 at 2
+  // blocks is the faster shape). Prefer the candidate with the most
+  // resident blocks, breaking ties toward more chains (rpt*ilp).
+  int rpt = 2;
+  bool rows_lds = true;
+  size_t lds = 0;
+  int best_blocks = 0;
+  {
+    struct Cand { int rpt, ilp; };
+    const Cand cands[] = {{2, ilp}, {1, ilp}, {2, 2}, {1, 2}};
+    int best_chains = 0;
+    bool found = false;
+    for (const Cand& cnd : cands) {
+      size_t nb = nodes_lds ? (size_t)cnd.ilp * max_nodes * 8 : 0;
+      size_t l = nb + (size_t)cnd.rpt * 256 * slabs * elem;
+      if (l > 150 * 1024) continue;
+      int blocks_cu = (int)std::min<size_t>(kMaxLds / std::max(l, (size_t)1),
+                                            3);
+      int chains = cnd.rpt * cnd.ilp;
+      if (blocks_cu > best_blocks ||
+          (blocks_cu == best_blocks && chains > best_chains)) {
+        best_blocks = blocks_cu;
+        best_chains = chains;
+        rpt = cnd.rpt;
+        ilp = cnd.ilp;
+        lds = l;
+        found = true;
+      }
+    }
+    if (!found) {  // rows exceed LDS even alone: global-X walk
+      rows_lds = false;
+      rpt = 1;
+      lds = nodes_lds ? (size_t)ilp * max_nodes * 8 : 0;
+    }
+  }
+  bool force_global = false;
+  if (const char* e = getenv("IFA_SCORE_FORCE_GLOBAL")) {
+    if (atoi(e)) {
+      force_global = true;
+      rows_lds = false;
+      rpt = 1;
+      lds = nodes_lds ? (size_t)ilp * max_nodes * 8 : 0;
+    }
+  }
+  c.rpt = rpt;
+  c.ilp = ilp;
+  c.rows_lds = rows_lds;
+  c.nodes_lds = nodes_lds;
+  c.lds = lds;
+
+  // heap records (score_forest_heap): 16-bit rows, rows and four trees of
+  // 2^(height+1) 4-byte slots in LDS, the last slab's byte offset within
+  // the record's low half. Same budget and the same preference as above;
+  // taken only where it holds at least the blocks the v4 candidate holds.
+  // IFA_SCORE_HEAP=0 keeps the v4 route (A/B inside one build); so do the
+  // other two switches, which name v4 instantiations.
+  bool heap_on = true;
+  if (const char* e = getenv("IFA_SCORE_HEAP")) heap_on = atoi(e) != 0;
+  if (heap_on && elem == 2 && rows_lds && nodes_lds && !force_global &&
+      !ilp_forced && height >= 1 && height <= 13) {
+    const size_t slots = (size_t)2 << height;
+    int hb = 0;
+    for (int r : {2, 1}) {
+      const size_t tile = (size_t)r * 256 * slabs * elem;
+      if (tile > 65536) continue;  // slab offsets are 16 bits
+      const size_t l = (size_t)4 * slots * 4 + tile;
+      if (l > 150 * 1024) continue;
+      const int blocks_cu = (int)std::min<size_t>(kMaxLds / l, 3);
+      if (blocks_cu > hb) {  // r = 2 first: ties go to more chains
+        hb = blocks_cu;
+        c.heap_rpt = r;
+        c.heap_lds = l;
+      }
+    }
+    c.heap = hb > 0 && hb >= best_blocks;
+  }
+  return c;
+}
+
 }  // namespace
 
 torch::Tensor bag_gather(torch::Tensor X, torch::Tensor bag_idx) {
@@ -334,10 +461,62 @@ torch::Tensor v4_level_order(torch::Tensor nodes_packed,
   return out;
 }
 
+// pre-order v4 records with 16-bit key thresholds -> the heap records
+// score_forest_heap walks (see v4_heap_order_kernel), laid out for the
+// instantiation pick_score_cfg chooses for (d, max_nodes, height)
+torch::Tensor v4_heap_order(torch::Tensor nodes_packed, torch::Tensor ncount,
+                            int64_t height, int64_t d) {
+  CHECK_CUDA(nodes_packed);
+  CHECK_CONTIG(nodes_packed);
+  CHECK_CUDA(ncount);
+  CHECK_CONTIG(ncount);
+  TORCH_CHECK(nodes_packed.dim() == 3 && nodes_packed.size(2) == 2 &&
+                  nodes_packed.scalar_type() == torch::kInt32,
+              "nodes must be packed int32 [Tpad, max_nodes, 2]");
+  TORCH_CHECK(ncount.scalar_type() == torch::kInt32 && ncount.dim() == 1 &&
+                  ncount.size(0) == nodes_packed.size(0),
+              "ncount must be int32 [Tpad]");
+  TORCH_CHECK(nodes_packed.size(1) >= 1 && nodes_packed.size(1) <= 32767,
+              "packed node ids are 15 bits");
+  const ScoreCfg cfg = pick_score_cfg(2, d, nodes_packed.size(1), height);
+  TORCH_CHECK(cfg.heap, "no heap route for d=", d, " max_nodes=",
+              nodes_packed.size(1), " height=", height);
+  auto out = torch::empty({nodes_packed.size(0), (int64_t)2 << height},
+                          nodes_packed.options());
+  if (nodes_packed.size(0) == 0) return out;
+  ifa::launch_v4_heap_order(nodes_packed.data_ptr<int32_t>(),
+                            ncount.data_ptr<int32_t>(),
+                            out.data_ptr<int32_t>(),
+                            (int32_t)nodes_packed.size(0),
+                            (int32_t)nodes_packed.size(1), (int32_t)height,
+                            cfg.heap_rpt * 256 * 2, current_stream());
+  return out;
+}
+
+// which kernel family score_forest runs for these shapes: "heap", "v4",
+// "v4_global_nodes" (nodes walked from L2) or "v4_global_rows" (rows too).
+// `layout` ("packed", "pitched", "feature_major") picks an entry point of
+// the same family, never another route.
+std::string score_route(const std::string& dtype, int64_t d,
+                        int64_t max_nodes, int64_t height,
+                        const std::string& layout) {
+  TORCH_CHECK(dtype == "bf16" || dtype == "f16" || dtype == "f32",
+              "dtype must be bf16, f16 or f32");
+  TORCH_CHECK(layout == "packed" || layout == "pitched" ||
+                  layout == "feature_major",
+              "layout must be packed, pitched or feature_major");
+  const ScoreCfg cfg =
+      pick_score_cfg(dtype == "f32" ? 4 : 2, d, max_nodes, height);
+  if (cfg.heap) return "heap";
+  if (!cfg.rows_lds) return "v4_global_rows";
+  return cfg.nodes_lds ? "v4" : "v4_global_nodes";
+}
+
 torch::Tensor score_forest(torch::Tensor X, torch::Tensor nodes_packed,
                            torch::Tensor ncount, int64_t num_trees,
                            int64_t height_limit, double c_norm,
-                           bool finalize) {
+                           bool finalize,
+                           c10::optional<torch::Tensor> heap) {
   CHECK_CUDA(X);
   CHECK_CUDA(nodes_packed);
   CHECK_CONTIG(nodes_packed);
@@ -350,67 +529,35 @@ torch::Tensor score_forest(torch::Tensor X, torch::Tensor nodes_packed,
   int64_t N = X.size(0), d = X.size(1);
   int64_t Tpad = nodes_packed.size(0), max_nodes = nodes_packed.size(1);
   TORCH_CHECK(Tpad % 8 == 0, "packed tree count must be padded to 8");
-  // staged-tree ILP: 4 (default) or 8; 8 halves the number of barrier-
-  // bounded staging phases at the cost of occupancy (A/B via env)
-  int ilp = 4;
-  if (const char* e = getenv("IFA_SCORE_ILP")) ilp = atoi(e) == 8 ? 8 : 4;
   TORCH_CHECK(d <= 4094, "scoring supports d <= 4094 (12-bit feature field "
                          "plus the leaf sentinel column)");
   auto out = torch::empty({N}, X.options().dtype(torch::kFloat32));
   if (N == 0) return out;
 
   const ifa::RowDtype dt = row_dtype(X);
-  const size_t elem = (size_t)ifa::row_elem_bytes(dt);
-  // feature-major key tile: d feature slabs plus the sentinel slab, each
-  // rows_per_block keys, lane-adjacent — no padding needed
-  const int64_t slabs = d + 1;
-  // deep forests (large maxSamples) overflow LDS node staging: walk nodes
-  // from global/L2 instead (NODES_LDS=false) — correct for any tree size
-  bool nodes_lds =
-      (size_t)2 * max_nodes * 8 + (size_t)256 * slabs * elem <= 150 * 1024;
-  // config search over (rpt, ilp): wide-d rows inflate the LDS row tile,
-  // so dropping staged-tree ILP to 2 can buy back a resident block
-  // (measured: d=128 went 1 block/CU at ILP=4 -> 124M rows/s; ILP=2 at 2
-  // blocks is the faster shape). Prefer the candidate with the most
-  // resident blocks, breaking ties toward more chains (rpt*ilp).
-  int rpt = 2;
-  bool rows_lds = true;
-  size_t lds = 0;
-  {
-    struct Cand { int rpt, ilp; };
-    const Cand cands[] = {{2, ilp}, {1, ilp}, {2, 2}, {1, 2}};
-    int best_blocks = 0, best_chains = 0;
-    bool found = false;
-    for (const Cand& cnd : cands) {
-      size_t nb = nodes_lds ? (size_t)cnd.ilp * max_nodes * 8 : 0;
-      size_t l = nb + (size_t)cnd.rpt * 256 * slabs * elem;
-      if (l > 150 * 1024) continue;
-      int blocks_cu = (int)std::min<size_t>(kMaxLds / std::max(l, (size_t)1),
-                                            3);
-      int chains = cnd.rpt * cnd.ilp;
-      if (blocks_cu > best_blocks ||
-          (blocks_cu == best_blocks && chains > best_chains)) {
-        best_blocks = blocks_cu;
-        best_chains = chains;
-        rpt = cnd.rpt;
-        ilp = cnd.ilp;
-        lds = l;
-        found = true;
-      }
-    }
-    if (!found) {  // rows exceed LDS even alone: global-X walk
-      rows_lds = false;
-      rpt = 1;
-      lds = nodes_lds ? (size_t)ilp * max_nodes * 8 : 0;
-    }
+  const ScoreCfg cfg = pick_score_cfg(ifa::row_elem_bytes(dt), d, max_nodes,
+                                      height_limit);
+  if (cfg.heap && heap.has_value()) {
+    const torch::Tensor& hp = *heap;
+    CHECK_CUDA(hp);
+    CHECK_CONTIG(hp);
+    TORCH_CHECK(hp.dim() == 2 && hp.scalar_type() == torch::kInt32 &&
+                    hp.size(0) == Tpad &&
+                    hp.size(1) == ((int64_t)2 << height_limit),
+                "heap records must be int32 [Tpad, 2^(height+1)]");
+    int blocks = (int)std::min<int64_t>(
+        (N + cfg.heap_rpt * 256 - 1) / (cfg.heap_rpt * 256), 8192);
+    ifa::launch_score_forest_heap(
+        dt, cfg.heap_rpt, X.data_ptr(),
+        hp.data_ptr<int32_t>(), out.data_ptr<float>(), N, (int32_t)d, xl.rs,
+        xl.cs, (int32_t)Tpad, (int32_t)height_limit, (float)num_trees,
+        (float)c_norm, finalize ? 1 : 0, cfg.heap_lds, blocks,
+        current_stream());
+    return out;
   }
-  if (const char* e = getenv("IFA_SCORE_FORCE_GLOBAL")) {
-    if (atoi(e)) {
-      rows_lds = false;
-      rpt = 1;
-      lds = nodes_lds ? (size_t)ilp * max_nodes * 8 : 0;
-    }
-  }
+  const int rpt = cfg.rpt, ilp = cfg.ilp;
+  const bool rows_lds = cfg.rows_lds, nodes_lds = cfg.nodes_lds;
+  const size_t lds = cfg.lds;
   int64_t rows_per_block = (int64_t)(rows_lds ? rpt : 1) * 256;
   int blocks = (int)std::min<int64_t>(
       (N + rows_per_block - 1) / rows_per_block, 8192);
@@ -955,7 +1102,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "build extended iTrees (K3-K5)");
   m.def("v4_level_order", &v4_level_order,
         "re-lay pre-order v4 node records in level order for score_forest");
-  m.def("score_forest", &score_forest, "batched path-length scoring (K6)");
+  m.def("v4_heap_order", &v4_heap_order,
+        "pre-order v4 node records -> 4-byte heap records (16-bit rows)");
+  m.def("score_route", &score_route,
+        "kernel family score_forest runs for (dtype, d, max_nodes, height, "
+        "layout)");
+  m.def("score_forest", &score_forest, "batched path-length scoring (K6)",
+        py::arg("X"), py::arg("nodes_packed"), py::arg("ncount"),
+        py::arg("num_trees"), py::arg("height_limit"), py::arg("c_norm"),
+        py::arg("finalize"), py::arg("heap") = py::none());
   m.def("score_extended_forest", &score_extended_forest,
         "batched EIF scoring (K7)");
   m.def("score_extended_sparse_v2", &score_extended_sparse_v2,

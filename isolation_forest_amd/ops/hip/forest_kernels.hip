@@ -16,6 +16,11 @@
 //    self-looping leaves => FIXED-trip walks with zero bookkeeping,
 //    2 rows x 4 staged trees = 8 chains/thread with batch-phased LDS reads
 //    (staggered lgkmcnt waits). Bitwise == cpu_engine.path_lengths.
+//  * score_forest_heap            — the same walk for bf16/fp16 rows over
+//    4-byte heap records (16-bit threshold | slab offset, implicit
+//    children; v4_heap_order_kernel): 5 VALU per visit instead of 7, half
+//    the staging traffic. score_forest_v4 keeps f32 rows, d >= 128, deep
+//    forests and the global fallbacks (bindings.cpp, pick_score_cfg).
 //  * score_extended_dense_v2      — K7 fast path (hyperplanes densified to
 //    D in {8,16,32,64} columns; f32 rows): rows resident in f32 REGISTERS
 //    across the whole tree loop, one tree's nodes+values+weights staged in
@@ -492,6 +497,9 @@ __global__ void __launch_bounds__(WAVE) build_extended_forest_kernel(
 // ---------------------------------------------------------------------------
 // standard scoring kernel (K6/K8) — v4
 //
+// (16-bit rows that fit it take the 4-byte heap records of
+// score_forest_heap, further down, made from the same packer output.)
+//
 // Node record is 8 bytes {uint32 w0, uint32 w1}, trees in LEVEL order
 // (v4_level_order_kernel below re-lays the packers' pre-order output once
 // per pack; left child = right_child - 1):
@@ -677,7 +685,8 @@ __device__ __forceinline__ int v4_tile_slot(int j) {
 // cost the packed 20M x 32 pass 0.3-0.5 % (profiles/strided.md). The packed
 // entry point exists only for rows and nodes staged in LDS at ILP 4, the
 // shape that pass runs; everything else has one entry point for all layouts.
-// More would push tools/native/ifa_score, which links every kernel, past the
+// More would push tools/native/ifa_score, which links every kernel of this
+// file but the heap-record ones, past the
 // 2048 KB that tools/lint_offline.py allows any file of the tree
 // (tests/test_timing_and_bench.py runs it after the build).
 template <typename KT, int RPT, bool ROWS_LDS, int V4_ILP, bool NODES_LDS,
@@ -895,6 +904,228 @@ __global__ void __launch_bounds__(256) score_forest_v4_packed(
   score_forest_v4_body<KT, RPT, true, V4_ILP, true, true>(
       X, nodes, ncnt, out, N, d, Tpad, max_nodes, height_limit, fT, c_norm,
       finalize, d, 1);
+}
+
+// ---------------------------------------------------------------------------
+// standard scoring, 16-bit rows — heap records
+//
+// For bf16/fp16 rows the key threshold is 16 bits wide (w1 = key << 16), and
+// a tree of height H fits the implicit layout (children of slot c are 2c and
+// 2c+1, root at slot 1, slot 0 unused) in 2^(H+1) slots, so the link is
+// redundant too. v4_heap_order_kernel turns the packers' pre-order v4
+// records into uint32 [Tpad][2^(H+1)]:
+//   internal, slot c:  thr16 << 16 | byte offset of the feature's slab in
+//                      the key tile (feature * RPT*256 * 2)
+//   leaf at depth < H: pass-through records down its always-right path to
+//                      level H-1: low half = the sentinel slab's offset,
+//                      whose key 0xFFFF is >= every threshold
+//   level H:           f32 bits of the leaf value (depth + c(numInstances)),
+//                      today's w1
+//   never reached:     0
+// The visit is ds_read_b32 record, ds_read_u16 key at rows_base + (rec &
+// 0xFFFF), a 16-bit compare against the high half, cur = 2*cur + (key >=
+// thr16) — the same `x < t goes left` as v4, NaN keys (0xFFFF) right. After
+// H visits every chain sits on level H; one more read gives the value. A
+// tree is a fixed 2^(H+1) * 4 bytes and trees are contiguous, so the stage
+// is one linear 16-byte copy with no node count to wait for. Sums are the
+// same f32 adds in the same tree order as v4: bitwise the same result.
+// The route (bindings.cpp, pick_score_cfg) needs 16-bit rows,
+// (d + 1) * RPT*256 * 2 <= 65536 and 4 * 2^(H+1) * 4 bytes of LDS next to
+// the tile; everything else stays on score_forest_v4.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(WAVE) v4_heap_order_kernel(
+    const int2* __restrict__ in,       // [Tpad][max_nodes] pre-order v4
+    const int32_t* __restrict__ ncnt,  // [Tpad]
+    uint32_t* __restrict__ out,        // [Tpad][2 << H]
+    int32_t max_nodes, int32_t H, int32_t slab_bytes) {
+  int16_t* st = (int16_t*)smem;  // [2 << H] slot -> pre-order index, -1 none
+  const int lane = threadIdx.x;
+  const int slots = 2 << H;
+  const int2* src = in + (int64_t)blockIdx.x * max_nodes;
+  uint32_t* dst = out + (int64_t)blockIdx.x * slots;
+  const int n = min(max(ncnt[blockIdx.x], 1), max_nodes);
+  if (lane == 0) {
+    st[1] = 0;
+    dst[0] = 0;
+  }
+  __syncthreads();
+  for (int k = 0; k < H; ++k) {
+    const int lo = 1 << k;
+    for (int c = lo + lane; c < 2 * lo; c += WAVE) {
+      const int old = st[c];
+      uint32_t rec = 0;
+      int l = -1, r = -1;
+      if (old >= 0) {
+        const int2 nd = src[old];
+        const int right = pn_right(nd.x);
+        // same test as v4_level_order_kernel: a leaf links to itself, and
+        // children outside the tree are not followed
+        const bool internal = right != old && right < n && old + 1 < n;
+        rec = (internal ? ((uint32_t)nd.y & 0xFFFF0000u) : 0u) |
+              ((uint32_t)(pn_feat(nd.x) * slab_bytes) & 0xFFFFu);
+        l = internal ? old + 1 : -1;
+        r = internal ? right : old;  // a leaf passes through to the right
+      }
+      dst[c] = rec;
+      st[2 * c] = (int16_t)l;
+      st[2 * c + 1] = (int16_t)r;
+    }
+    __syncthreads();  // the next level's st[] entries are written
+  }
+  for (int c = (1 << H) + lane; c < slots; c += WAVE) {
+    const int old = st[c];
+    dst[c] = old >= 0 ? (uint32_t)src[old].y : 0u;
+  }
+}
+
+// Stage one block's rows into the v4 key tile: the staging of
+// score_forest_v4_body, which keeps its own copy inline so that its code
+// does not move. The caller puts a barrier on either side.
+template <typename KT, int RPT, bool PACKED>
+__device__ __forceinline__ void v4_stage_tile(KT* rows,
+                                              const KT* __restrict__ X,
+                                              int64_t block_row0,
+                                              int rows_here, int32_t d,
+                                              int64_t rs, int64_t cs) {
+  constexpr int FS = RPT * 256;
+  constexpr int EPV = 16 / (int)sizeof(KT);
+  const int tid = threadIdx.x;
+  const bool vec = cs == 1 && d % EPV == 0 && rs % EPV == 0 &&
+                   ((uintptr_t)X & 15) == 0;
+#pragma unroll
+  for (int r = 0; r < RPT; ++r) {
+    const int j = tid + r * 256;
+    KT* dst = rows + v4_tile_slot<KT, RPT>(j);
+    if (j < rows_here) {
+      const KT* src = X + (block_row0 + j) * rs;
+      if (vec) {
+        for (int c = 0; c < d; c += EPV) {
+          union { uint4 v; KT e[EPV]; } pc;
+          pc.v = *(const uint4*)(src + c);
+#pragma unroll
+          for (int k = 0; k < EPV; ++k)
+            dst[(c + k) * FS] = key_of_bits<KT>(pc.e[k]);
+        }
+      } else {
+        if (PACKED) {
+          for (int c = 0; c < d; ++c)
+            dst[c * FS] = key_of_bits<KT>(src[c]);
+        } else {
+          for (int c = 0; c < d; ++c, src += cs)
+            dst[c * FS] = key_of_bits<KT>(*src);
+        }
+      }
+    } else {
+      // tail block: rows past N are walked but never stored
+      for (int c = 0; c < d; ++c) dst[c * FS] = key_sentinel<KT>();
+    }
+    dst[d * FS] = key_sentinel<KT>();  // leaf sentinel slab
+  }
+}
+
+// Four trees are staged per barrier phase; each thread walks RPT rows x 4
+// trees, as in score_forest_v4.
+template <typename KT, int RPT, bool PACKED>
+__global__ void __launch_bounds__(256) score_forest_heap(
+    const KT* __restrict__ X,           // raw bf16/fp16 bits
+    const uint32_t* __restrict__ heap,  // [Tpad][2 << H] heap records
+    float* __restrict__ out,            // [N] (path sum or score)
+    int64_t N, int32_t d, int32_t Tpad, int32_t H, float fT, float c_norm,
+    int32_t finalize, int64_t rs_, int64_t cs_) {
+  static_assert(sizeof(KT) == 2, "heap records hold 16-bit thresholds");
+  constexpr int ILP = 4;
+  const int tid = threadIdx.x;
+  const int rows_per_iter = RPT * 256;
+  const int64_t rs = PACKED ? (int64_t)d : rs_;
+  const int64_t cs = PACKED ? (int64_t)1 : cs_;
+  const int slots = 2 << H;
+
+  uint32_t* tlds = (uint32_t*)smem;  // [ILP * slots]
+  KT* rows = (KT*)(tlds + ILP * slots);
+
+  for (int64_t block_row0 = (int64_t)blockIdx.x * rows_per_iter; block_row0 < N;
+       block_row0 += (int64_t)gridDim.x * rows_per_iter) {
+    const int rows_here = (int)min((int64_t)rows_per_iter, N - block_row0);
+
+    __syncthreads();  // previous iteration's readers done
+    v4_stage_tile<KT, RPT, PACKED>(rows, X, block_row0, rows_here, d, rs, cs);
+    // the first stage's leading barrier orders these stores before the walk
+
+    const char* rb[RPT];
+#pragma unroll
+    for (int r = 0; r < RPT; ++r)
+      rb[r] = (const char*)(rows + v4_tile_slot<KT, RPT>(tid + r * 256));
+
+    float psum[RPT];
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) psum[r] = 0.f;
+
+    for (int t = 0; t < Tpad; t += ILP) {
+      __syncthreads();
+      {
+        // ILP * slots >= 16 words, so both sides stay 16-byte aligned
+        const uint4* src = (const uint4*)(heap + (int64_t)t * slots);
+        uint4* dst = (uint4*)tlds;
+        const int nvec = ILP * slots / 4;
+        for (int i = tid; i < nvec; i += 256) dst[i] = src[i];
+      }
+      __syncthreads();
+
+      uint32_t cur[RPT][ILP];
+#pragma unroll
+      for (int r = 0; r < RPT; ++r)
+#pragma unroll
+        for (int s = 0; s < ILP; ++s) cur[r][s] = 1;
+
+      // one level of all RPT*ILP chains, reads batched as in v4
+      auto visit = [&]() __attribute__((always_inline)) {
+        uint32_t rec[RPT][ILP];
+#pragma unroll
+        for (int r = 0; r < RPT; ++r)
+#pragma unroll
+          for (int s = 0; s < ILP; ++s) rec[r][s] = tlds[s * slots + cur[r][s]];
+        uint32_t key[RPT][ILP];
+#pragma unroll
+        for (int r = 0; r < RPT; ++r)
+#pragma unroll
+          for (int s = 0; s < ILP; ++s)
+            key[r][s] =
+                *(const uint16_t*)(rb[r] + (rec[r][s] & 0xFFFFu));
+#pragma unroll
+        for (int r = 0; r < RPT; ++r)
+#pragma unroll
+          for (int s = 0; s < ILP; ++s)
+            cur[r][s] = 2 * cur[r][s] + (key[r][s] >= (rec[r][s] >> 16));
+      };
+      int it = 0;
+      for (; it + 2 <= H; it += 2) {
+        visit();
+        visit();
+      }
+      if (it < H) visit();
+      // every chain sits on level H: the slot holds depth + c(m)
+#pragma unroll
+      for (int r = 0; r < RPT; ++r)
+#pragma unroll
+        for (int s = 0; s < ILP; ++s)
+          psum[r] = __fadd_rn(
+              psum[r], __uint_as_float(tlds[s * slots + cur[r][s]]));
+    }
+
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+      const int64_t my_row = block_row0 + tid + r * 256;
+      if (my_row < N) {
+        if (finalize) {
+          const float mean32 = (float)((double)psum[r] / (double)fT);
+          const double ratio = (double)mean32 / (double)c_norm;
+          out[my_row] = (float)exp2(-ratio);
+        } else {
+          out[my_row] = psum[r];
+        }
+      }
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -2079,6 +2310,52 @@ void launch_v4_level_order(const void* nodes, const int32_t* ncount,
                      (size_t)max_nodes * 2, stream, (const int2*)nodes, ncount,
                      (int2*)out, max_nodes);
 }
+
+void launch_v4_heap_order(const void* nodes, const int32_t* ncount,
+                          void* out, int32_t Tpad, int32_t max_nodes,
+                          int32_t height, int32_t slab_bytes,
+                          hipStream_t stream) {
+  hipLaunchKernelGGL(v4_heap_order_kernel, dim3(Tpad), dim3(WAVE),
+                     (size_t)(2 << height) * 2, stream, (const int2*)nodes,
+                     ncount, (uint32_t*)out, max_nodes, height, slab_bytes);
+}
+
+// 16-bit rows only (ROW_BF16 / ROW_F16); rpt 1 or 2.
+// tools/native/ifa_score stays on the level-order route (bitwise the same
+// scores) and is built with IFA_NO_HEAP_ROUTE: with these instantiations
+// linked in, the binary passes the 2048 KB tools/lint_offline.py allows.
+#ifndef IFA_NO_HEAP_ROUTE
+void launch_score_forest_heap(RowDtype dt, int rpt, const void* X,
+                              const void* heap, float* out, int64_t N,
+                              int32_t d, int64_t rs, int64_t cs, int32_t Tpad,
+                              int32_t height, float fT, float c_norm,
+                              int finalize, size_t lds, int blocks,
+                              hipStream_t stream) {
+  const bool packed = rs == d && cs == 1;
+#define LH1(KT, RPT, PK)                                                      \
+  do {                                                                        \
+    raise_lds((const void*)score_forest_heap<KT, RPT, PK>, lds);              \
+    hipLaunchKernelGGL((score_forest_heap<KT, RPT, PK>), dim3(blocks),        \
+                       dim3(256), lds, stream, (const KT*)X,                  \
+                       (const uint32_t*)heap, out, N, d, Tpad, height, fT,    \
+                       c_norm, finalize, rs, cs);                             \
+  } while (0)
+#define LH(KT, RPT)                                                           \
+  do {                                                                        \
+    if (packed) LH1(KT, RPT, true);                                           \
+    else LH1(KT, RPT, false);                                                 \
+  } while (0)
+  if (dt == ROW_BF16) {
+    if (rpt == 2) LH(uint16_t, 2);
+    else LH(uint16_t, 1);
+  } else {
+    if (rpt == 2) LH(f16_t, 2);
+    else LH(f16_t, 1);
+  }
+#undef LH
+#undef LH1
+}
+#endif  // IFA_NO_HEAP_ROUTE
 
 void launch_score_forest(RowDtype dt, int rpt, bool rows_lds, bool nodes_lds,
                          int ilp, const void* X, const void* nodes,

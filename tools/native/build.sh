@@ -2,7 +2,10 @@
 # Build the standalone native scorer for gfx950 (cross-compiles without a GPU).
 set -e
 cd "$(dirname "$0")/../.."
+# IFA_NO_HEAP_ROUTE: the CLI scores on the level-order v4 route and leaves
+# the heap-record instantiations out (binary size cap, tools/lint_offline.py)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off \
+  -DIFA_NO_HEAP_ROUTE \
   tools/native/ifa_score.cpp \
   isolation_forest_amd/ops/hip/forest_kernels.hip \
   -Iisolation_forest_amd/ops/hip -lz -o tools/native/ifa_score
