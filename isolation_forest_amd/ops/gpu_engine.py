@@ -970,6 +970,26 @@ def _v4_heap_records(aos: torch.Tensor, ncount: torch.Tensor, d: int, kind,
                              int(height), int(d))
 
 
+def _heap_rpt(aos: torch.Tensor, d: int, kind, height: int) -> int:
+    """Rows per thread of the heap instantiation these shapes run now (0 off
+    the heap route). The records' slab offsets are laid out for it."""
+    from . import load_extension as _packing_extension
+
+    return int(_packing_extension().score_heap_cfg(
+        _row_kind(kind), int(d), int(aos.shape[1]), int(height))[1])
+
+
+def _heap_for_call(aos, extra, d: int, kind):
+    """extra["heap"] where it was laid out for the rows per thread this call
+    runs. IFA_HEAP_PHASE set after the pack was made can move that choice;
+    the call then takes the level-order records (same scores)."""
+    heap = extra["heap"]
+    if heap is None:
+        return None
+    now = _heap_rpt(aos, d, kind, max(extra["height"], 1))
+    return heap if now == extra["heap_rpt"] else None
+
+
 def _device_forest(model, device, v4_key=None):
     """Cached device copy of the packed forest. v4_key = (d, kind) selects
     the standard-scoring v4 packing; None = the EIF packing. Packs that
@@ -1066,6 +1086,8 @@ def _device_forest(model, device, v4_key=None):
             aos = torch.from_numpy(packed).to(device)
             extra["heap"] = _v4_heap_records(aos, ncount, v4_key[1],
                                              v4_key[2], max(max_depth, 1))
+            extra["heap_rpt"] = _heap_rpt(aos, v4_key[1], v4_key[2],
+                                          max(max_depth, 1))
             aos = _v4_walk_order(aos, ncount)
             extra["height"] = max_depth
         elif isinstance(v4_key, tuple) and v4_key[0] == "explain":
@@ -1125,6 +1147,7 @@ def _device_forest(model, device, v4_key=None):
                 aos = torch.from_numpy(packed).to(device)
                 ncount = torch.from_numpy(ncount_np).to(device)
             extra["heap"] = _v4_heap_records(aos, ncount, d, kind, max_depth)
+            extra["heap_rpt"] = _heap_rpt(aos, d, kind, max_depth)
             aos = _v4_walk_order(aos, ncount)
             extra["height"] = max_depth
         else:
@@ -1174,7 +1197,7 @@ def score_forest(model, X: torch.Tensor, finalize: bool = True) -> torch.Tensor:
     aos, ncount, extra = _device_forest(model, X.device, v4_key=(d, kind))
     return ext.score_forest(
         _rows_in_place(X), aos, ncount, forest.num_trees, extra["height"], c,
-        finalize, extra["heap"],
+        finalize, _heap_for_call(aos, extra, d, kind),
     )
 
 
@@ -1223,7 +1246,7 @@ def score_extended_forest(model, X: torch.Tensor, finalize: bool = True) -> torc
             model, X.device, v4_key=("eif0", d, _row_kind(X.dtype)))
         return ext.score_forest(
             _rows_in_place(X), aos, ncount, forest.num_trees, extra["height"],
-            c, finalize, extra["heap"],
+            c, finalize, _heap_for_call(aos, extra, d, X.dtype),
         )
     if nnz <= 5 and _eif_uniform_nnz(forest):
         elem = 4 if X.dtype == torch.float32 else 2  # bf16 / fp16

@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "row_dtype.h"
@@ -47,7 +48,7 @@ void launch_v4_heap_order(const void* nodes, const int32_t* ncount,
                           int32_t height, int32_t slab_bytes,
                           hipStream_t stream);
 
-void launch_score_forest_heap(RowDtype dt, int rpt, const void* X,
+void launch_score_forest_heap(RowDtype dt, int rpt, int phase, const void* X,
                               const void* heap, float* out, int64_t N,
                               int32_t d, int64_t rs, int64_t cs, int32_t Tpad,
                               int32_t height, float fT, float c_norm,
@@ -230,7 +231,7 @@ struct ScoreCfg {
   size_t lds;
   // score_forest_heap: taken when `heap` and the caller has the records
   bool heap;
-  int heap_rpt;
+  int heap_rpt, heap_phase;
   size_t heap_lds;
 };
 
@@ -305,31 +306,54 @@ ScoreCfg pick_score_cfg(int elem_bytes, int64_t d, int64_t max_nodes,
   c.nodes_lds = nodes_lds;
   c.lds = lds;
 
-  // heap records (score_forest_heap): 16-bit rows, rows and four trees of
-  // 2^(height+1) 4-byte slots in LDS, the last slab's byte offset within
-  // the record's low half. Same budget and the same preference as above;
-  // taken only where it holds at least the blocks the v4 candidate holds.
+  // heap records (score_forest_heap): 16-bit rows, rows and one barrier
+  // phase of trees (4 or 8, 2^(height+1) 4-byte slots each) in LDS, the
+  // last slab's byte offset within the record's low half. Same budget and
+  // the same preference as above; taken only where it holds at least the
+  // blocks the v4 candidate holds. The 8-tree phase halves the barriers and
+  // is taken where its best candidate keeps at least the resident blocks of
+  // the 4-tree one; it may choose another RPT than the 4-tree phase would
+  // (the larger stage moves the RPT bound), and v4_heap_order lays the
+  // records out for the RPT chosen here.
   // IFA_SCORE_HEAP=0 keeps the v4 route (A/B inside one build); so do the
-  // other two switches, which name v4 instantiations.
+  // other two switches, which name v4 instantiations. IFA_HEAP_PHASE=4|8
+  // picks the phase where that phase is routable; any other value is
+  // ignored.
   bool heap_on = true;
   if (const char* e = getenv("IFA_SCORE_HEAP")) heap_on = atoi(e) != 0;
+  int phase_want = 0;
+  if (const char* e = getenv("IFA_HEAP_PHASE")) {
+    const int v = atoi(e);
+    if (v == 4 || v == 8) phase_want = v;
+  }
   if (heap_on && elem == 2 && rows_lds && nodes_lds && !force_global &&
       !ilp_forced && height >= 1 && height <= 13) {
     const size_t slots = (size_t)2 << height;
-    int hb = 0;
-    for (int r : {2, 1}) {
-      const size_t tile = (size_t)r * 256 * slabs * elem;
-      if (tile > 65536) continue;  // slab offsets are 16 bits
-      const size_t l = (size_t)4 * slots * 4 + tile;
-      if (l > 150 * 1024) continue;
-      const int blocks_cu = (int)std::min<size_t>(kMaxLds / l, 3);
-      if (blocks_cu > hb) {  // r = 2 first: ties go to more chains
-        hb = blocks_cu;
-        c.heap_rpt = r;
-        c.heap_lds = l;
+    struct HeapCand { int blocks, rpt; size_t lds; };
+    auto best_of = [&](int phase) {
+      HeapCand h{0, 0, 0};
+      for (int r : {2, 1}) {
+        const size_t tile = (size_t)r * 256 * slabs * elem;
+        if (tile > 65536) continue;  // slab offsets are 16 bits
+        const size_t l = (size_t)phase * slots * 4 + tile;
+        if (l > 150 * 1024) continue;
+        const int blocks_cu = (int)std::min<size_t>(kMaxLds / l, 3);
+        if (blocks_cu > h.blocks) {  // r = 2 first: ties go to more chains
+          h.blocks = blocks_cu;
+          h.rpt = r;
+          h.lds = l;
+        }
       }
-    }
-    c.heap = hb > 0 && hb >= best_blocks;
+      return h;
+    };
+    const HeapCand h4 = best_of(4), h8 = best_of(8);
+    const bool can8 = h8.blocks > 0 && h8.blocks >= h4.blocks;
+    const bool take8 = can8 && phase_want != 4;
+    const HeapCand& h = take8 ? h8 : h4;
+    c.heap_phase = take8 ? 8 : 4;
+    c.heap_rpt = h.rpt;
+    c.heap_lds = h.lds;
+    c.heap = h.blocks > 0 && h.blocks >= best_blocks;
   }
   return c;
 }
@@ -512,6 +536,19 @@ std::string score_route(const std::string& dtype, int64_t d,
   return cfg.nodes_lds ? "v4" : "v4_global_nodes";
 }
 
+// (trees per barrier phase, rows per thread) of the heap instantiation
+// these shapes run, or (0, 0) where score_route is not "heap"
+std::pair<int64_t, int64_t> score_heap_cfg(const std::string& dtype,
+                                           int64_t d, int64_t max_nodes,
+                                           int64_t height) {
+  TORCH_CHECK(dtype == "bf16" || dtype == "f16" || dtype == "f32",
+              "dtype must be bf16, f16 or f32");
+  const ScoreCfg cfg =
+      pick_score_cfg(dtype == "f32" ? 4 : 2, d, max_nodes, height);
+  if (!cfg.heap) return {0, 0};
+  return {cfg.heap_phase, cfg.heap_rpt};
+}
+
 torch::Tensor score_forest(torch::Tensor X, torch::Tensor nodes_packed,
                            torch::Tensor ncount, int64_t num_trees,
                            int64_t height_limit, double c_norm,
@@ -548,7 +585,7 @@ torch::Tensor score_forest(torch::Tensor X, torch::Tensor nodes_packed,
     int blocks = (int)std::min<int64_t>(
         (N + cfg.heap_rpt * 256 - 1) / (cfg.heap_rpt * 256), 8192);
     ifa::launch_score_forest_heap(
-        dt, cfg.heap_rpt, X.data_ptr(),
+        dt, cfg.heap_rpt, cfg.heap_phase, X.data_ptr(),
         hp.data_ptr<int32_t>(), out.data_ptr<float>(), N, (int32_t)d, xl.rs,
         xl.cs, (int32_t)Tpad, (int32_t)height_limit, (float)num_trees,
         (float)c_norm, finalize ? 1 : 0, cfg.heap_lds, blocks,
@@ -1107,6 +1144,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("score_route", &score_route,
         "kernel family score_forest runs for (dtype, d, max_nodes, height, "
         "layout)");
+  m.def("score_heap_cfg", &score_heap_cfg,
+        "(trees per phase, rows per thread) of the heap walk for (dtype, d, "
+        "max_nodes, height); (0, 0) off the heap route");
   m.def("score_forest", &score_forest, "batched path-length scoring (K6)",
         py::arg("X"), py::arg("nodes_packed"), py::arg("ncount"),
         py::arg("num_trees"), py::arg("height_limit"), py::arg("c_norm"),

@@ -18,8 +18,11 @@
 //    (staggered lgkmcnt waits). Bitwise == cpu_engine.path_lengths.
 //  * score_forest_heap            — the same walk for bf16/fp16 rows over
 //    4-byte heap records (16-bit threshold | slab offset, implicit
-//    children; v4_heap_order_kernel): 5 VALU per visit instead of 7, half
-//    the staging traffic. score_forest_v4 keeps f32 rows, d >= 128, deep
+//    children; v4_heap_order_kernel): half the staging traffic, and 4 VALU
+//    per visit instead of 7 (complemented slot index over trees staged
+//    reversed in LDS: node address, key address, subtract, funnel shift).
+//    8 trees per barrier phase, all walked together, where they fit next to
+//    the tile; else 4. score_forest_v4 keeps f32 rows, d >= 128, deep
 //    forests and the global fallbacks (bindings.cpp, pick_score_cfg).
 //  * score_extended_dense_v2      — K7 fast path (hyperplanes densified to
 //    D in {8,16,32,64} columns; f32 rows): rows resident in f32 REGISTERS
@@ -924,14 +927,15 @@ __global__ void __launch_bounds__(256) score_forest_v4_packed(
 //   never reached:     0
 // The visit is ds_read_b32 record, ds_read_u16 key at rows_base + (rec &
 // 0xFFFF), a 16-bit compare against the high half, cur = 2*cur + (key >=
-// thr16) — the same `x < t goes left` as v4, NaN keys (0xFFFF) right. After
+// thr16) — the same `x < t goes left` as v4, NaN keys (0xFFFF) right (the
+// kernel computes it on the complemented slot, see score_forest_heap). After
 // H visits every chain sits on level H; one more read gives the value. A
 // tree is a fixed 2^(H+1) * 4 bytes and trees are contiguous, so the stage
 // is one linear 16-byte copy with no node count to wait for. Sums are the
 // same f32 adds in the same tree order as v4: bitwise the same result.
 // The route (bindings.cpp, pick_score_cfg) needs 16-bit rows,
-// (d + 1) * RPT*256 * 2 <= 65536 and 4 * 2^(H+1) * 4 bytes of LDS next to
-// the tile; everything else stays on score_forest_v4.
+// (d + 1) * RPT*256 * 2 <= 65536 and 4 or 8 trees of 2^(H+1) * 4 bytes in
+// LDS next to the tile; everything else stays on score_forest_v4.
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(WAVE) v4_heap_order_kernel(
     const int2* __restrict__ in,       // [Tpad][max_nodes] pre-order v4
@@ -1023,9 +1027,21 @@ __device__ __forceinline__ void v4_stage_tile(KT* rows,
   }
 }
 
-// Four trees are staged per barrier phase; each thread walks RPT rows x 4
-// trees, as in score_forest_v4.
-template <typename KT, int RPT, bool PACKED>
+// PH trees (4 or 8) are staged per barrier phase and walked together: each
+// thread keeps RPT rows x PH trees in flight (16 chains at RPT = 2, PH = 8).
+//
+// The walk tracks the complemented slot n = ~cur (n = ~1 at the root). With
+// x = key - thr16 in 32 bits (both below 65536, so no overflow) bit 31 of x
+// is `key < thr16`, and cur' = 2*cur + 1 - lt is ~cur' = 2*~cur + lt: one
+// subtract and one funnel shift, n' = (n:x) >> 31, where the direct form
+// needs a compare, a select and a shift-or. A pass-through record has thr16
+// = 0 and the sentinel key 0xFFFF, so x >= 0 and it still goes right. To
+// keep the node address one shift-add, every tree is staged REVERSED: word c
+// of the global tree sits at word slots-1-c of its LDS window, which is
+// tree_end + 4*n bytes with n read as a negative int. The global records
+// are untouched. Reversal maps a byte address a to const - a, a bijection on
+// banks.
+template <typename KT, int RPT, bool PACKED, int PH>
 __global__ void __launch_bounds__(256) score_forest_heap(
     const KT* __restrict__ X,           // raw bf16/fp16 bits
     const uint32_t* __restrict__ heap,  // [Tpad][2 << H] heap records
@@ -1033,15 +1049,18 @@ __global__ void __launch_bounds__(256) score_forest_heap(
     int64_t N, int32_t d, int32_t Tpad, int32_t H, float fT, float c_norm,
     int32_t finalize, int64_t rs_, int64_t cs_) {
   static_assert(sizeof(KT) == 2, "heap records hold 16-bit thresholds");
-  constexpr int ILP = 4;
+  static_assert(PH == 4 || PH == 8, "4 or 8 trees per barrier phase");
+  constexpr int ILP = PH;
   const int tid = threadIdx.x;
   const int rows_per_iter = RPT * 256;
   const int64_t rs = PACKED ? (int64_t)d : rs_;
   const int64_t cs = PACKED ? (int64_t)1 : cs_;
   const int slots = 2 << H;
+  // 16-byte vectors per tree: slots / 4 = 1 << (H - 1), H >= 1
+  const int vmask = (1 << (H - 1)) - 1;
 
-  uint32_t* tlds = (uint32_t*)smem;  // [ILP * slots]
-  KT* rows = (KT*)(tlds + ILP * slots);
+  uint32_t* tlds = (uint32_t*)smem;  // [PH * slots], each tree reversed
+  KT* rows = (KT*)(tlds + PH * slots);
 
   for (int64_t block_row0 = (int64_t)blockIdx.x * rows_per_iter; block_row0 < N;
        block_row0 += (int64_t)gridDim.x * rows_per_iter) {
@@ -1060,22 +1079,39 @@ __global__ void __launch_bounds__(256) score_forest_heap(
 #pragma unroll
     for (int r = 0; r < RPT; ++r) psum[r] = 0.f;
 
-    for (int t = 0; t < Tpad; t += ILP) {
+    // end of tree s's window: slot c is tend[s][~c]
+    const uint32_t* tend[ILP];
+#pragma unroll
+    for (int s = 0; s < ILP; ++s) tend[s] = tlds + (s + 1) * slots;
+
+    for (int t = 0; t < Tpad; t += PH) {
+      // Tpad is a multiple of 4, not necessarily of PH: the last phase may
+      // hold half as many trees. The copy stops at tree Tpad - 1; the
+      // windows past it are filled with 0, which walks like a padding tree
+      // (slab 0, threshold 0) and adds 0.0f
+      const int nt = min(PH, Tpad - t);
       __syncthreads();
       {
-        // ILP * slots >= 16 words, so both sides stay 16-byte aligned
+        // nt * slots >= 16 words, so both sides stay 16-byte aligned. Vector
+        // j of a tree goes to vector (slots/4 - 1 - j) of the same tree with
+        // its words swapped end for end: i ^ vmask flips j and keeps the tree
         const uint4* src = (const uint4*)(heap + (int64_t)t * slots);
         uint4* dst = (uint4*)tlds;
-        const int nvec = ILP * slots / 4;
-        for (int i = tid; i < nvec; i += 256) dst[i] = src[i];
+        const int nvec = nt * (slots / 4);
+        for (int i = tid; i < nvec; i += 256) {
+          const uint4 v = src[i];
+          dst[i ^ vmask] = make_uint4(v.w, v.z, v.y, v.x);
+        }
+        for (int i = nvec + tid; i < PH * (slots / 4); i += 256)
+          dst[i] = make_uint4(0u, 0u, 0u, 0u);
       }
       __syncthreads();
 
-      uint32_t cur[RPT][ILP];
+      uint32_t n[RPT][ILP];
 #pragma unroll
       for (int r = 0; r < RPT; ++r)
 #pragma unroll
-        for (int s = 0; s < ILP; ++s) cur[r][s] = 1;
+        for (int s = 0; s < ILP; ++s) n[r][s] = ~1u;
 
       // one level of all RPT*ILP chains, reads batched as in v4
       auto visit = [&]() __attribute__((always_inline)) {
@@ -1083,7 +1119,8 @@ __global__ void __launch_bounds__(256) score_forest_heap(
 #pragma unroll
         for (int r = 0; r < RPT; ++r)
 #pragma unroll
-          for (int s = 0; s < ILP; ++s) rec[r][s] = tlds[s * slots + cur[r][s]];
+          for (int s = 0; s < ILP; ++s)
+            rec[r][s] = tend[s][(int32_t)n[r][s]];
         uint32_t key[RPT][ILP];
 #pragma unroll
         for (int r = 0; r < RPT; ++r)
@@ -1095,7 +1132,8 @@ __global__ void __launch_bounds__(256) score_forest_heap(
         for (int r = 0; r < RPT; ++r)
 #pragma unroll
           for (int s = 0; s < ILP; ++s)
-            cur[r][s] = 2 * cur[r][s] + (key[r][s] >= (rec[r][s] >> 16));
+            n[r][s] = __builtin_amdgcn_alignbit(
+                n[r][s], key[r][s] - (rec[r][s] >> 16), 31);
       };
       int it = 0;
       for (; it + 2 <= H; it += 2) {
@@ -1109,7 +1147,7 @@ __global__ void __launch_bounds__(256) score_forest_heap(
 #pragma unroll
         for (int s = 0; s < ILP; ++s)
           psum[r] = __fadd_rn(
-              psum[r], __uint_as_float(tlds[s * slots + cur[r][s]]));
+              psum[r], __uint_as_float(tend[s][(int32_t)n[r][s]]));
     }
 
 #pragma unroll
@@ -2320,25 +2358,30 @@ void launch_v4_heap_order(const void* nodes, const int32_t* ncount,
                      ncount, (uint32_t*)out, max_nodes, height, slab_bytes);
 }
 
-// 16-bit rows only (ROW_BF16 / ROW_F16); rpt 1 or 2.
+// 16-bit rows only (ROW_BF16 / ROW_F16); rpt 1 or 2; phase 4 or 8 trees.
 // tools/native/ifa_score stays on the level-order route (bitwise the same
 // scores) and is built with IFA_NO_HEAP_ROUTE: with these instantiations
 // linked in, the binary passes the 2048 KB tools/lint_offline.py allows.
 #ifndef IFA_NO_HEAP_ROUTE
-void launch_score_forest_heap(RowDtype dt, int rpt, const void* X,
+void launch_score_forest_heap(RowDtype dt, int rpt, int phase, const void* X,
                               const void* heap, float* out, int64_t N,
                               int32_t d, int64_t rs, int64_t cs, int32_t Tpad,
                               int32_t height, float fT, float c_norm,
                               int finalize, size_t lds, int blocks,
                               hipStream_t stream) {
   const bool packed = rs == d && cs == 1;
-#define LH1(KT, RPT, PK)                                                      \
+#define LH2(KT, RPT, PK, PH)                                                  \
   do {                                                                        \
-    raise_lds((const void*)score_forest_heap<KT, RPT, PK>, lds);              \
-    hipLaunchKernelGGL((score_forest_heap<KT, RPT, PK>), dim3(blocks),        \
+    raise_lds((const void*)score_forest_heap<KT, RPT, PK, PH>, lds);          \
+    hipLaunchKernelGGL((score_forest_heap<KT, RPT, PK, PH>), dim3(blocks),    \
                        dim3(256), lds, stream, (const KT*)X,                  \
                        (const uint32_t*)heap, out, N, d, Tpad, height, fT,    \
                        c_norm, finalize, rs, cs);                             \
+  } while (0)
+#define LH1(KT, RPT, PK)                                                      \
+  do {                                                                        \
+    if (phase == 8) LH2(KT, RPT, PK, 8);                                      \
+    else LH2(KT, RPT, PK, 4);                                                 \
   } while (0)
 #define LH(KT, RPT)                                                           \
   do {                                                                        \
@@ -2354,6 +2397,7 @@ void launch_score_forest_heap(RowDtype dt, int rpt, const void* X,
   }
 #undef LH
 #undef LH1
+#undef LH2
 }
 #endif  // IFA_NO_HEAP_ROUTE
 
