@@ -7,7 +7,11 @@
 #include <torch/extension.h>
 
 #include <algorithm>
+#include <climits>
+#include <map>
+#include <mutex>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -48,12 +52,16 @@ void launch_v4_heap_order(const void* nodes, const int32_t* ncount,
                           int32_t height, int32_t slab_bytes,
                           hipStream_t stream);
 
-void launch_score_forest_heap(RowDtype dt, int rpt, int phase, const void* X,
-                              const void* heap, float* out, int64_t N,
-                              int32_t d, int64_t rs, int64_t cs, int32_t Tpad,
-                              int32_t height, float fT, float c_norm,
-                              int finalize, size_t lds, int blocks,
-                              hipStream_t stream);
+hipError_t launch_score_forest_heap(RowDtype dt, int rpt, int phase,
+                                    int threads, const void* X,
+                                    const void* heap, float* out, int64_t N,
+                                    int32_t d, int64_t rs, int64_t cs,
+                                    int32_t Tpad, int32_t height, float fT,
+                                    float c_norm, int finalize, size_t lds,
+                                    int blocks, hipStream_t stream);
+
+int score_forest_heap_resident(RowDtype dt, int rpt, bool packed, int phase,
+                               int threads, size_t lds);
 
 void launch_score_forest(RowDtype dt, int rpt, bool rows_lds, bool nodes_lds,
                          int ilp, const void* X, const void* nodes,
@@ -230,10 +238,41 @@ struct ScoreCfg {
   bool rows_lds, nodes_lds;
   size_t lds;
   // score_forest_heap: taken when `heap` and the caller has the records
+  // heap_rpt is tile rows / 256 (what the records' slab offsets are laid
+  // out for); heap_threads (256 or 512) share the tile's rows out
   bool heap;
-  int heap_rpt, heap_phase;
+  int heap_rpt, heap_phase, heap_threads;
   size_t heap_lds;
 };
+
+// Blocks per CU that every 512-thread heap instantiation of `phase` (bf16
+// and fp16, packed and strided) keeps resident at this LDS size: the least
+// of the runtime's four occupancy figures, asked once per (device, phase,
+// size) and one map lookup after that. pick_score_cfg runs on every score
+// call, and the first may fall inside a stream capture: the function
+// attribute and the occupancy query are host-side and put nothing on a
+// stream, so they are safe there.
+int heap_wide_resident(int phase, size_t lds) {
+  static std::mutex mu;
+  static std::map<std::tuple<int, int, size_t>, int> memo;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  const auto key = std::make_tuple(dev, phase, lds);
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = memo.find(key);
+  if (it == memo.end()) {
+    int least = INT_MAX;
+    for (ifa::RowDtype dt : {ifa::ROW_BF16, ifa::ROW_F16})
+      for (bool packed : {true, false})
+        least = std::min(least, ifa::score_forest_heap_resident(
+                                    dt, 1, packed, phase, 512, lds));
+    it = memo.emplace(key, least).first;
+  }
+  return it->second;
+}
 
 ScoreCfg pick_score_cfg(int elem_bytes, int64_t d, int64_t max_nodes,
                         int64_t height) {
@@ -319,6 +358,11 @@ ScoreCfg pick_score_cfg(int elem_bytes, int64_t d, int64_t max_nodes,
   // other two switches, which name v4 instantiations. IFA_HEAP_PHASE=4|8
   // picks the phase where that phase is routable; any other value is
   // ignored.
+  // A 512-row tile is walked by 512 threads with one row each (8 waves per
+  // block in the same LDS) where every 512-thread instantiation of the
+  // phase keeps the blocks counted here resident, by the runtime's own
+  // occupancy figure; IFA_HEAP_WAVES=4|8 picks the block size where both
+  // are routable (any other value is ignored). The records are the same.
   bool heap_on = true;
   if (const char* e = getenv("IFA_SCORE_HEAP")) heap_on = atoi(e) != 0;
   int phase_want = 0;
@@ -354,6 +398,15 @@ ScoreCfg pick_score_cfg(int elem_bytes, int64_t d, int64_t max_nodes,
     c.heap_rpt = h.rpt;
     c.heap_lds = h.lds;
     c.heap = h.blocks > 0 && h.blocks >= best_blocks;
+    c.heap_threads = 256;
+    int waves_want = 0;
+    if (const char* e = getenv("IFA_HEAP_WAVES")) {
+      const int v = atoi(e);
+      if (v == 4 || v == 8) waves_want = v;
+    }
+    if (c.heap && h.rpt == 2 && waves_want != 4 &&
+        heap_wide_resident(c.heap_phase, h.lds) >= h.blocks)
+      c.heap_threads = 512;
   }
   return c;
 }
@@ -549,6 +602,17 @@ std::pair<int64_t, int64_t> score_heap_cfg(const std::string& dtype,
   return {cfg.heap_phase, cfg.heap_rpt};
 }
 
+// threads per block of the heap instantiation these shapes run (256, or 512
+// where a 512-row tile is walked one row per thread), 0 off the heap route
+int64_t score_heap_block(const std::string& dtype, int64_t d,
+                         int64_t max_nodes, int64_t height) {
+  TORCH_CHECK(dtype == "bf16" || dtype == "f16" || dtype == "f32",
+              "dtype must be bf16, f16 or f32");
+  const ScoreCfg cfg =
+      pick_score_cfg(dtype == "f32" ? 4 : 2, d, max_nodes, height);
+  return cfg.heap ? cfg.heap_threads : 0;
+}
+
 torch::Tensor score_forest(torch::Tensor X, torch::Tensor nodes_packed,
                            torch::Tensor ncount, int64_t num_trees,
                            int64_t height_limit, double c_norm,
@@ -582,14 +646,29 @@ torch::Tensor score_forest(torch::Tensor X, torch::Tensor nodes_packed,
                     hp.size(0) == Tpad &&
                     hp.size(1) == ((int64_t)2 << height_limit),
                 "heap records must be int32 [Tpad, 2^(height+1)]");
-    int blocks = (int)std::min<int64_t>(
-        (N + cfg.heap_rpt * 256 - 1) / (cfg.heap_rpt * 256), 8192);
-    ifa::launch_score_forest_heap(
-        dt, cfg.heap_rpt, cfg.heap_phase, X.data_ptr(),
+    // rows per thread of the instantiation: the tile's rows over its threads
+    const int rpt = cfg.heap_rpt * 256 / cfg.heap_threads;
+    const int64_t tiles = (N + cfg.heap_rpt * 256 - 1) / (cfg.heap_rpt * 256);
+    // 8192 blocks at the most. A grid of one block per resident slot, or a
+    // small multiple of that, was measured: it lost, or (10 per slot) did
+    // not clear the noise rule (profiles/score_waves.md).
+    // IFA_HEAP_MAX_BLOCKS=<n> lowers the limit so that tests reach the
+    // grid-stride loop at small N.
+    int64_t max_blocks = 8192;
+    if (const char* e = getenv("IFA_HEAP_MAX_BLOCKS")) {
+      const int64_t v = atoll(e);
+      if (v >= 1) max_blocks = std::min<int64_t>(v, 8192);
+    }
+    int blocks = (int)std::min<int64_t>(tiles, max_blocks);
+    const hipError_t err = ifa::launch_score_forest_heap(
+        dt, rpt, cfg.heap_phase, cfg.heap_threads, X.data_ptr(),
         hp.data_ptr<int32_t>(), out.data_ptr<float>(), N, (int32_t)d, xl.rs,
         xl.cs, (int32_t)Tpad, (int32_t)height_limit, (float)num_trees,
         (float)c_norm, finalize ? 1 : 0, cfg.heap_lds, blocks,
         current_stream());
+    TORCH_CHECK(err == hipSuccess, "score_forest_heap launch failed (",
+                cfg.heap_threads, " threads, ", cfg.heap_lds, " B of LDS): ",
+                hipGetErrorString(err));
     return out;
   }
   const int rpt = cfg.rpt, ilp = cfg.ilp;
@@ -1144,6 +1223,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("score_route", &score_route,
         "kernel family score_forest runs for (dtype, d, max_nodes, height, "
         "layout)");
+  m.def("score_heap_block", &score_heap_block,
+        "threads per block of the heap instantiation (0 off the heap route)",
+        py::arg("dtype"), py::arg("d"), py::arg("max_nodes"),
+        py::arg("height"));
   m.def("score_heap_cfg", &score_heap_cfg,
         "(trees per phase, rows per thread) of the heap walk for (dtype, d, "
         "max_nodes, height); (0, 0) off the heap route");

@@ -675,7 +675,9 @@ __global__ void __launch_bounds__(WAVE) v4_level_order_kernel(
 // element offset of block row j inside one slab of the v4 key tile. 32-bit
 // keys: element j. 16-bit keys: P = RPT*128 words per slab, row j in word
 // (j mod P), half (j / P) — RPT=2 pairs rows tid and tid+256 in one word,
-// RPT=1 pairs rows tid and tid+128.
+// RPT=1 pairs rows tid and tid+128. RPT here is tile rows / 256: the heap
+// walk's 512-thread blocks pass 2 for their one row per thread, so a 512-row
+// tile has one map however its rows are shared out among threads.
 template <typename KT, int RPT>
 __device__ __forceinline__ int v4_tile_slot(int j) {
   if (sizeof(KT) == 4) return j;
@@ -984,22 +986,24 @@ __global__ void __launch_bounds__(WAVE) v4_heap_order_kernel(
 
 // Stage one block's rows into the v4 key tile: the staging of
 // score_forest_v4_body, which keeps its own copy inline so that its code
-// does not move. The caller puts a barrier on either side.
-template <typename KT, int RPT, bool PACKED>
+// does not move. The caller puts a barrier on either side. BT threads stage
+// RPT rows each: thread tid owns rows tid, tid + BT, ... of the RPT*BT-row
+// tile, whose slot map depends on the tile's size alone.
+template <typename KT, int RPT, bool PACKED, int BT>
 __device__ __forceinline__ void v4_stage_tile(KT* rows,
                                               const KT* __restrict__ X,
                                               int64_t block_row0,
                                               int rows_here, int32_t d,
                                               int64_t rs, int64_t cs) {
-  constexpr int FS = RPT * 256;
+  constexpr int FS = RPT * BT;
   constexpr int EPV = 16 / (int)sizeof(KT);
   const int tid = threadIdx.x;
   const bool vec = cs == 1 && d % EPV == 0 && rs % EPV == 0 &&
                    ((uintptr_t)X & 15) == 0;
 #pragma unroll
   for (int r = 0; r < RPT; ++r) {
-    const int j = tid + r * 256;
-    KT* dst = rows + v4_tile_slot<KT, RPT>(j);
+    const int j = tid + r * BT;
+    KT* dst = rows + v4_tile_slot<KT, RPT * BT / 256>(j);
     if (j < rows_here) {
       const KT* src = X + (block_row0 + j) * rs;
       if (vec) {
@@ -1041,8 +1045,14 @@ __device__ __forceinline__ void v4_stage_tile(KT* rows,
 // tree_end + 4*n bytes with n read as a negative int. The global records
 // are untouched. Reversal maps a byte address a to const - a, a bijection on
 // banks.
-template <typename KT, int RPT, bool PACKED, int PH>
-__global__ void __launch_bounds__(256) score_forest_heap(
+//
+// BT threads per block (256 or 512) walk a tile of RPT*BT rows. A 512-row
+// tile is the same LDS, the same slot map and the same records whether 256
+// threads own two rows each or 512 threads one: the second form puts twice
+// the waves on a CU for the same chains in flight (bindings.cpp,
+// pick_score_cfg, takes it where the register file holds them all).
+template <typename KT, int RPT, bool PACKED, int PH, int BT>
+__global__ void __launch_bounds__(BT) score_forest_heap(
     const KT* __restrict__ X,           // raw bf16/fp16 bits
     const uint32_t* __restrict__ heap,  // [Tpad][2 << H] heap records
     float* __restrict__ out,            // [N] (path sum or score)
@@ -1050,9 +1060,10 @@ __global__ void __launch_bounds__(256) score_forest_heap(
     int32_t finalize, int64_t rs_, int64_t cs_) {
   static_assert(sizeof(KT) == 2, "heap records hold 16-bit thresholds");
   static_assert(PH == 4 || PH == 8, "4 or 8 trees per barrier phase");
+  static_assert(BT == 256 || BT == 512, "4 or 8 waves per block");
   constexpr int ILP = PH;
   const int tid = threadIdx.x;
-  const int rows_per_iter = RPT * 256;
+  const int rows_per_iter = RPT * BT;
   const int64_t rs = PACKED ? (int64_t)d : rs_;
   const int64_t cs = PACKED ? (int64_t)1 : cs_;
   const int slots = 2 << H;
@@ -1067,13 +1078,15 @@ __global__ void __launch_bounds__(256) score_forest_heap(
     const int rows_here = (int)min((int64_t)rows_per_iter, N - block_row0);
 
     __syncthreads();  // previous iteration's readers done
-    v4_stage_tile<KT, RPT, PACKED>(rows, X, block_row0, rows_here, d, rs, cs);
+    v4_stage_tile<KT, RPT, PACKED, BT>(rows, X, block_row0, rows_here, d, rs,
+                                       cs);
     // the first stage's leading barrier orders these stores before the walk
 
     const char* rb[RPT];
 #pragma unroll
     for (int r = 0; r < RPT; ++r)
-      rb[r] = (const char*)(rows + v4_tile_slot<KT, RPT>(tid + r * 256));
+      rb[r] = (const char*)(rows +
+                            v4_tile_slot<KT, RPT * BT / 256>(tid + r * BT));
 
     float psum[RPT];
 #pragma unroll
@@ -1098,11 +1111,11 @@ __global__ void __launch_bounds__(256) score_forest_heap(
         const uint4* src = (const uint4*)(heap + (int64_t)t * slots);
         uint4* dst = (uint4*)tlds;
         const int nvec = nt * (slots / 4);
-        for (int i = tid; i < nvec; i += 256) {
+        for (int i = tid; i < nvec; i += BT) {
           const uint4 v = src[i];
           dst[i ^ vmask] = make_uint4(v.w, v.z, v.y, v.x);
         }
-        for (int i = nvec + tid; i < PH * (slots / 4); i += 256)
+        for (int i = nvec + tid; i < PH * (slots / 4); i += BT)
           dst[i] = make_uint4(0u, 0u, 0u, 0u);
       }
       __syncthreads();
@@ -1152,7 +1165,7 @@ __global__ void __launch_bounds__(256) score_forest_heap(
 
 #pragma unroll
     for (int r = 0; r < RPT; ++r) {
-      const int64_t my_row = block_row0 + tid + r * 256;
+      const int64_t my_row = block_row0 + tid + r * BT;
       if (my_row < N) {
         if (finalize) {
           const float mean32 = (float)((double)psum[r] / (double)fT);
@@ -2358,46 +2371,66 @@ void launch_v4_heap_order(const void* nodes, const int32_t* ncount,
                      ncount, (uint32_t*)out, max_nodes, height, slab_bytes);
 }
 
-// 16-bit rows only (ROW_BF16 / ROW_F16); rpt 1 or 2; phase 4 or 8 trees.
+// 16-bit rows only (ROW_BF16 / ROW_F16); rpt 1 or 2; phase 4 or 8 trees;
+// threads 256, or 512 with rpt 1.
 // tools/native/ifa_score stays on the level-order route (bitwise the same
 // scores) and is built with IFA_NO_HEAP_ROUTE: with these instantiations
 // linked in, the binary passes the 2048 KB tools/lint_offline.py allows.
 #ifndef IFA_NO_HEAP_ROUTE
-void launch_score_forest_heap(RowDtype dt, int rpt, int phase, const void* X,
-                              const void* heap, float* out, int64_t N,
-                              int32_t d, int64_t rs, int64_t cs, int32_t Tpad,
-                              int32_t height, float fT, float c_norm,
-                              int finalize, size_t lds, int blocks,
-                              hipStream_t stream) {
-  const bool packed = rs == d && cs == 1;
-#define LH2(KT, RPT, PK, PH)                                                  \
-  do {                                                                        \
-    raise_lds((const void*)score_forest_heap<KT, RPT, PK, PH>, lds);          \
-    hipLaunchKernelGGL((score_forest_heap<KT, RPT, PK, PH>), dim3(blocks),    \
-                       dim3(256), lds, stream, (const KT*)X,                  \
-                       (const uint32_t*)heap, out, N, d, Tpad, height, fT,    \
-                       c_norm, finalize, rs, cs);                             \
-  } while (0)
-#define LH1(KT, RPT, PK)                                                      \
-  do {                                                                        \
-    if (phase == 8) LH2(KT, RPT, PK, 8);                                      \
-    else LH2(KT, RPT, PK, 4);                                                 \
-  } while (0)
-#define LH(KT, RPT)                                                           \
-  do {                                                                        \
-    if (packed) LH1(KT, RPT, true);                                           \
-    else LH1(KT, RPT, false);                                                 \
-  } while (0)
-  if (dt == ROW_BF16) {
-    if (rpt == 2) LH(uint16_t, 2);
-    else LH(uint16_t, 1);
-  } else {
-    if (rpt == 2) LH(f16_t, 2);
-    else LH(f16_t, 1);
+namespace {
+// the instantiation (dt, rpt, packed, phase, threads) names, as a host
+// function pointer
+const void* score_forest_heap_fn(RowDtype dt, int rpt, bool packed, int phase,
+                                 int threads) {
+#define HF2(KT, RPT, PK, PH, BT)                                              \
+  ((const void*)score_forest_heap<KT, RPT, PK, PH, BT>)
+#define HF1(KT, RPT, BT)                                                      \
+  (packed ? (phase == 8 ? HF2(KT, RPT, true, 8, BT)                           \
+                        : HF2(KT, RPT, true, 4, BT))                          \
+          : (phase == 8 ? HF2(KT, RPT, false, 8, BT)                          \
+                        : HF2(KT, RPT, false, 4, BT)))
+#define HF(KT)                                                                \
+  (threads == 512 ? HF1(KT, 1, 512)                                           \
+                  : (rpt == 2 ? HF1(KT, 2, 256) : HF1(KT, 1, 256)))
+  return dt == ROW_BF16 ? HF(uint16_t) : HF(f16_t);
+#undef HF
+#undef HF1
+#undef HF2
+}
+}  // namespace
+
+// blocks of `threads` threads with `lds` bytes each that one CU keeps
+// resident for this instantiation (registers, LDS and wave slots together),
+// as the runtime reports it; 0 where it cannot say
+int score_forest_heap_resident(RowDtype dt, int rpt, bool packed, int phase,
+                               int threads, size_t lds) {
+  const void* fn = score_forest_heap_fn(dt, rpt, packed, phase, threads);
+  raise_lds(fn, lds);
+  int n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, threads, lds) !=
+      hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
   }
-#undef LH
-#undef LH1
-#undef LH2
+  return n;
+}
+
+// returns the launch's status for the caller to check
+hipError_t launch_score_forest_heap(RowDtype dt, int rpt, int phase,
+                                    int threads, const void* X,
+                                    const void* heap, float* out, int64_t N,
+                                    int32_t d, int64_t rs, int64_t cs,
+                                    int32_t Tpad, int32_t height, float fT,
+                                    float c_norm, int finalize, size_t lds,
+                                    int blocks, hipStream_t stream) {
+  const bool packed = rs == d && cs == 1;
+  const void* fn = score_forest_heap_fn(dt, rpt, packed, phase, threads);
+  raise_lds(fn, lds);
+  // every instantiation has this signature but for the row pointer's type
+  const uint32_t* hp = (const uint32_t*)heap;
+  void* args[] = {&X, &hp, &out, &N, &d, &Tpad, &height, &fT, &c_norm,
+                  &finalize, &rs, &cs};
+  return hipLaunchKernel(fn, dim3(blocks), dim3(threads), args, lds, stream);
 }
 #endif  // IFA_NO_HEAP_ROUTE
 
