@@ -43,9 +43,16 @@ class ExtendedIsolationForest(IsolationForest):
         if X.is_cuda:
             import logging
 
+            from ..ops import gpu_engine
+
+            if gpu_engine.large_build_fits(X, rp.num_samples):
+                return gpu_engine.build_extended_forest_large(
+                    X, bag_idx, feat_sub, seed, rp, tree_id_offset=t_lo
+                )
             logging.getLogger(__name__).warning(
-                "maxSamples %d exceeds the GPU build cap (16384); building "
-                "trees on CPU (scoring stays on GPU)", rp.num_samples,
+                "maxSamples %d over %d rows exceeds the GPU build's 32-bit "
+                "row ids; building trees on CPU (scoring stays on GPU)",
+                rp.num_samples, X.shape[0],
             )
             X = X.float().cpu()
         Xc = X.contiguous().float().numpy()

@@ -135,12 +135,18 @@ class IsolationForest:
                 X, bag_idx, feat_sub, seed, rp, tree_id_offset=t_lo
             )
         if X.is_cuda:
-            # GPU build kernel caps bags at 16384 rows (LDS row-index
-            # staging); larger bags build on the CPU oracle (bit-identical
-            # semantics) and score through the GPU wide-format kernel
+            from ..ops import gpu_engine
+
+            # past the LDS kernels' 16384-row bags: the multi-wave builders,
+            # which keep the row ids in global memory and read X in place
+            if gpu_engine.large_build_fits(X, rp.num_samples):
+                return gpu_engine.build_forest_large(
+                    X, bag_idx, feat_sub, seed, rp, tree_id_offset=t_lo
+                )
             logger.warning(
-                "maxSamples %d exceeds the GPU build cap (16384); building "
-                "trees on CPU (scoring stays on GPU)", rp.num_samples,
+                "maxSamples %d over %d rows exceeds the GPU build's 32-bit "
+                "row ids; building trees on CPU (scoring stays on GPU)",
+                rp.num_samples, X.shape[0],
             )
             X = X.float().cpu()
         Xc = X.contiguous().float().numpy()

@@ -4,7 +4,10 @@ The canonical forest lives in host numpy (core/forest.py) — it is small
 (MBs) next to the data (GBs-TBs). Bags/feature subsets are drawn host-side
 with the same Philox counters the kernels use, so a GPU-built forest is
 BIT-IDENTICAL to the CPU oracle's for the same seed (tests/test_gpu.py
-enforces this).
+enforces this). Bags of up to 16384 rows build with the one-wave LDS kernels
+(build_forest / build_extended_forest); larger ones with the multi-wave
+global-memory kernels (build_forest_large / build_extended_forest_large),
+which read X in place and give the same forest.
 
 Scoring packs (the v4 integer-key node format, EIF dense/sparse variants)
 are built ON DEVICE with torch ops from the raw build outputs (depths come
@@ -186,6 +189,175 @@ def build_extended_forest(X: torch.Tensor, bag_idx: np.ndarray,
     }
     fr.depth_np = depth.cpu().numpy()
     return fr
+
+
+# ---------------------------------------------------------------------------
+# large-bag builds (maxSamples > 16384)
+# ---------------------------------------------------------------------------
+
+# Device bytes one launch of a large builder may allocate next to X: the row-id
+# scratch (8 * n per tree), the chunk's int64 bag indices (8 * n per tree) and
+# its raw outputs (max_nodes * (28 [+ 8 * nnz]) per tree). Trees are built in
+# chunks that fit (always at least one tree); chunks are tree shards, which
+# concatenate bitwise. 8 GiB keeps a standard 1M-row bag at ~150 trees per
+# launch on a 288 GB card and leaves the matrix its memory.
+BUILD_LARGE_BUDGET_BYTES = 8 << 30
+
+# Threads per tree block of the large builders (profiles/build_large.md).
+BUILD_LARGE_THREADS = 256
+
+
+def large_build_fits(X: torch.Tensor, n: int) -> bool:
+    """Whether the large builders take bags of ``n`` rows of ``X``: they keep
+    row ids as uint32 and node ids as int32 (the bindings check the same)."""
+    return int(X.shape[0]) <= 1 << 32 and n <= 1 << 30
+
+
+def _large_chunk_trees(T: int, per_tree_bytes: int, chunk_trees) -> int:
+    if chunk_trees is None:
+        chunk_trees = BUILD_LARGE_BUDGET_BYTES // max(per_tree_bytes, 1)
+    chunk_trees = int(chunk_trees)
+    if chunk_trees < 1:
+        if chunk_trees < 0:
+            raise ValueError("chunk_trees must be positive")
+        chunk_trees = 1
+    return min(T, chunk_trees)
+
+
+def _large_threads() -> int:
+    v = os.environ.get("IFA_BUILD_LARGE_THREADS")
+    return int(v) if v else BUILD_LARGE_THREADS
+
+
+def build_forest_large(X: torch.Tensor, bag_idx: np.ndarray,
+                       feat_sub: np.ndarray, seed: int, rp,
+                       tree_id_offset: int = 0, chunk_trees=None,
+                       return_depth: bool = False):
+    """``build_forest`` for bags of any size (the models use it above the
+    LDS builders' 16384 rows): rows are read in place from ``X``, no f32
+    ``[T, n, d]`` gather is made, and the trees are built ``chunk_trees`` at
+    a time (``None``: as many as ``BUILD_LARGE_BUDGET_BYTES`` holds). The
+    forest is bitwise ``cpu_engine.build_forest``'s. It carries no device
+    tensors: forests this size score through the host-packed wide formats.
+    ``return_depth=True`` returns ``(forest, depth)`` with the kernel's
+    per-node depths ``[T, max_nodes]``."""
+    ext = load_extension()
+    device = X.device
+    n = rp.num_samples
+    height_limit = int(math.ceil(math.log2(max(n, 2))))
+    max_nodes = 2 * n - 1
+    T = int(bag_idx.shape[0])
+    Xr = _rows_in_place(X)
+    lut = _leaf_lut(n, device)
+    fs = np.ascontiguousarray(feat_sub, dtype=np.int32)
+    chunk = _large_chunk_trees(T, 16 * n + 28 * max_nodes, chunk_trees)
+    f_np = np.empty((T, max_nodes), dtype=np.int32)
+    v_np = np.empty((T, max_nodes), dtype=np.float32)
+    r_np = np.empty((T, max_nodes), dtype=np.int32)
+    c_np = np.empty((T, max_nodes), dtype=np.int64)
+    nc_np = np.empty((T,), dtype=np.int32)
+    d_np = np.empty((T, max_nodes), dtype=np.int32) if return_depth else None
+    for lo in range(0, T, chunk):
+        hi = min(T, lo + chunk)
+        bag_t = torch.from_numpy(np.ascontiguousarray(bag_idx[lo:hi])).to(device)
+        fs_t = torch.from_numpy(fs[lo:hi]).to(device)
+        feat, value, right, count, ncount, depth = ext.build_forest_large(
+            Xr, bag_t, fs_t, seed, tree_id_offset + lo, lut, max_nodes,
+            height_limit, _large_threads())
+        f_np[lo:hi] = feat.cpu().numpy()
+        v_np[lo:hi] = value.cpu().numpy()
+        r_np[lo:hi] = right.cpu().numpy()
+        c_np[lo:hi] = count.cpu().numpy()
+        nc_np[lo:hi] = ncount.cpu().numpy()
+        if return_depth:
+            d_np[lo:hi] = depth.cpu().numpy()
+        del bag_t, fs_t, feat, value, right, count, ncount, depth
+    _mask_padding(f_np, r_np, c_np, nc_np, Forest.PAD)
+    v_np = np.where(f_np >= 0, v_np, np.where(f_np == Forest.LEAF, v_np, 0.0)).astype(
+        np.float32
+    )
+    forest = Forest(
+        feature=f_np,
+        value=v_np,
+        right=r_np,
+        num_instances=c_np,
+        node_count=nc_np,
+        num_samples=n,
+        num_features=rp.num_features,
+        total_num_features=rp.total_features,
+        value64=np.where(f_np >= 0, v_np, 0.0).astype(np.float64),
+    )
+    return (forest, d_np) if return_depth else forest
+
+
+def build_extended_forest_large(X: torch.Tensor, bag_idx: np.ndarray,
+                                feat_sub: np.ndarray, seed: int, rp,
+                                tree_id_offset: int = 0, chunk_trees=None,
+                                return_depth: bool = False):
+    """``build_extended_forest`` for bags of any size; see
+    ``build_forest_large``."""
+    ext = load_extension()
+    device = X.device
+    n = rp.num_samples
+    height_limit = int(math.ceil(math.log2(max(n, 2))))
+    max_nodes = 2 ** (height_limit + 1) - 1
+    nnz = min(rp.extension_level + 1, rp.num_features)
+    T = int(bag_idx.shape[0])
+    Xr = _rows_in_place(X)
+    lut = _leaf_lut(n, device)
+    fs = np.ascontiguousarray(feat_sub, dtype=np.int32)
+    chunk = _large_chunk_trees(
+        T, 16 * n + (28 + 8 * nnz) * max_nodes, chunk_trees)
+    f_np = np.empty((T, max_nodes), dtype=np.int32)
+    v_np = np.empty((T, max_nodes), dtype=np.float32)
+    r_np = np.empty((T, max_nodes), dtype=np.int32)
+    c_np = np.empty((T, max_nodes), dtype=np.int64)
+    nc_np = np.empty((T,), dtype=np.int32)
+    hidx_np = np.empty((T, max_nodes, nnz), dtype=np.int32)
+    hw_np = np.empty((T, max_nodes, nnz), dtype=np.float32)
+    off64_np = np.empty((T, max_nodes), dtype=np.float64)
+    d_np = np.empty((T, max_nodes), dtype=np.int32) if return_depth else None
+    for lo in range(0, T, chunk):
+        hi = min(T, lo + chunk)
+        bag_t = torch.from_numpy(np.ascontiguousarray(bag_idx[lo:hi])).to(device)
+        fs_t = torch.from_numpy(fs[lo:hi]).to(device)
+        (feat, value, right, count, ncount, hidx, hw, off64,
+         depth) = ext.build_extended_forest_large(
+            Xr, bag_t, fs_t, seed, tree_id_offset + lo, lut, nnz, max_nodes,
+            height_limit, _large_threads())
+        f_np[lo:hi] = feat.cpu().numpy()
+        v_np[lo:hi] = value.cpu().numpy()
+        r_np[lo:hi] = right.cpu().numpy()
+        c_np[lo:hi] = count.cpu().numpy()
+        nc_np[lo:hi] = ncount.cpu().numpy()
+        hidx_np[lo:hi] = hidx.cpu().numpy()
+        hw_np[lo:hi] = hw.cpu().numpy()
+        off64_np[lo:hi] = off64.cpu().numpy()
+        if return_depth:
+            d_np[lo:hi] = depth.cpu().numpy()
+        del (bag_t, fs_t, feat, value, right, count, ncount, hidx, hw, off64,
+             depth)
+    live = _mask_padding(f_np, r_np, c_np, nc_np, ExtendedForest.PAD)
+    v_np = np.where(live, v_np, 0.0).astype(np.float32)
+    internal = (f_np >= 0) & live
+    hidx_np[~internal] = 0
+    hw_np[~internal] = 0.0
+    off64_np[~internal] = 0.0
+    fr = ExtendedForest(
+        feature=f_np,
+        value=v_np,
+        right=r_np,
+        num_instances=c_np,
+        node_count=nc_np,
+        hyper_idx=hidx_np,
+        hyper_w=hw_np,
+        offset64=off64_np,
+        num_samples=n,
+        num_features=rp.num_features,
+        total_num_features=rp.total_features,
+        extension_level=rp.extension_level,
+    )
+    return (fr, d_np) if return_depth else fr
 
 
 # ---------------------------------------------------------------------------

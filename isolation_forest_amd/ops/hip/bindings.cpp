@@ -43,6 +43,26 @@ void launch_build_extended_forest(const float* bags, const int32_t* feat_sub,
                                   int32_t max_nodes, int32_t height_limit,
                                   size_t lds, hipStream_t stream);
 
+void launch_build_forest_large(RowDtype dt, const void* X, int64_t rs,
+                               int64_t cs, const int64_t* bag_idx,
+                               uint32_t* scratch, const int32_t* feat_sub,
+                               int32_t* feat, float* value, int32_t* right,
+                               int32_t* count, int32_t* ncount, int32_t* depth,
+                               const float* leaf_lut, uint64_t seed,
+                               int32_t tree_id_offset, int32_t T, int32_t n,
+                               int32_t k, int32_t max_nodes,
+                               int32_t height_limit, int threads, size_t lds,
+                               hipStream_t stream);
+
+void launch_build_extended_forest_large(
+    RowDtype dt, const void* X, int64_t rs, int64_t cs, const int64_t* bag_idx,
+    uint32_t* scratch, const int32_t* feat_sub, int32_t* feat, float* value,
+    int32_t* right, int32_t* count, int32_t* ncount, int32_t* hidx, float* hw,
+    double* off64, int32_t* depth, const float* leaf_lut, uint64_t seed,
+    int32_t tree_id_offset, int32_t T, int32_t n, int32_t k, int32_t nnz,
+    int32_t max_nodes, int32_t height_limit, int threads, size_t lds,
+    hipStream_t stream);
+
 void launch_v4_level_order(const void* nodes, const int32_t* ncount,
                            void* out, int32_t Tpad, int32_t max_nodes,
                            hipStream_t stream);
@@ -509,6 +529,167 @@ std::vector<torch::Tensor> build_extended_forest(
       leaf_lut.data_ptr<float>(), (uint64_t)seed, (int32_t)tree_id_offset,
       (int32_t)T, (int32_t)n, (int32_t)d, (int32_t)k, (int32_t)nnz,
       (int32_t)max_nodes, (int32_t)height_limit, lds, current_stream());
+  return {feat, value, right, count, ncount, hidx, hw, off64, depth};
+}
+
+// ---------------------------------------------------------------------------
+// large-bag builds (n > 16384): rows read in place from X, row ids in a
+// global scratch of 8 * n bytes per tree (the caller chunks the trees)
+// ---------------------------------------------------------------------------
+
+namespace {
+
+struct LargeBuildShape {
+  int64_t T, n, d, k;
+  XLayout xl;
+};
+
+// Admission shared by the two large builders: everything the kernels index
+// with must fit its type, and every index they read must be in range.
+LargeBuildShape check_large_build(const torch::Tensor& X,
+                                  const torch::Tensor& bag_idx,
+                                  const torch::Tensor& feat_sub,
+                                  const torch::Tensor& leaf_lut,
+                                  int64_t tree_id_offset, int64_t max_nodes,
+                                  int64_t height_limit, int64_t nnz,
+                                  bool extended, int64_t threads) {
+  CHECK_CUDA(X);
+  CHECK_CUDA(bag_idx);
+  CHECK_CONTIG(bag_idx);
+  CHECK_CUDA(feat_sub);
+  CHECK_CONTIG(feat_sub);
+  CHECK_CUDA(leaf_lut);
+  CHECK_CONTIG(leaf_lut);
+  check_x(X);
+  LargeBuildShape s;
+  s.xl = check_x_layout(X);
+  TORCH_CHECK(bag_idx.dim() == 2 && bag_idx.scalar_type() == torch::kInt64,
+              "bag_idx must be int64 [T, n]");
+  TORCH_CHECK(feat_sub.dim() == 2 && feat_sub.scalar_type() == torch::kInt32 &&
+                  feat_sub.size(0) == bag_idx.size(0),
+              "feat_sub must be int32 [T, k]");
+  s.T = bag_idx.size(0);
+  s.n = bag_idx.size(1);
+  s.d = X.size(1);
+  s.k = feat_sub.size(1);
+  const int64_t N = X.size(0);
+  TORCH_CHECK(s.T >= 1 && s.T <= INT_MAX &&
+                  s.T + tree_id_offset <= (int64_t)INT_MAX &&
+                  tree_id_offset >= 0,
+              "tree ids must fit int32");
+  // row ids are kept as uint32, segment bounds and 2n-1 node ids as 32-bit
+  TORCH_CHECK(N >= 1 && N <= ((int64_t)1 << 32),
+              "large GPU build keeps 32-bit row ids: N must be <= 2^32");
+  TORCH_CHECK(s.n >= 1 && s.n <= ((int64_t)1 << 30),
+              "large GPU build supports maxSamples <= 2^30");
+  TORCH_CHECK(height_limit >= 0 && height_limit <= 30, "height_limit > 30");
+  TORCH_CHECK(max_nodes >= 1 && max_nodes <= (int64_t)INT_MAX,
+              "max_nodes must fit int32 node ids");
+  // the most nodes a tree can emit: a full binary tree of the height limit,
+  // and for standard trees (no empty sides) also 2n-1
+  const int64_t full = ((int64_t)2 << height_limit) - 1;
+  const int64_t need = extended ? full : std::min(full, 2 * s.n - 1);
+  TORCH_CHECK(max_nodes >= need, "max_nodes ", max_nodes,
+              " cannot hold a tree of up to ", need, " nodes");
+  // avail[] holds feature ids as int32
+  TORCH_CHECK(s.d >= 1 && s.d <= (int64_t)INT_MAX, "d must fit int32");
+  TORCH_CHECK(s.k >= 1 && s.k <= s.d, "k must be in [1, d]");
+  TORCH_CHECK(nnz >= 1 && nnz <= s.k, "nnz must be in [1, k]");
+  TORCH_CHECK(max_nodes <= INT64_MAX / s.T / nnz,
+              "T * max_nodes * nnz overflows int64");
+  TORCH_CHECK(leaf_lut.scalar_type() == torch::kFloat32 &&
+                  leaf_lut.numel() >= s.n + 1,
+              "leaf_lut must be float32 [n + 1]");
+  TORCH_CHECK(threads >= 64 && threads <= 512 && threads % 64 == 0,
+              "threads must be a multiple of 64 in [64, 512]");
+  // one reduction each; a bad index would otherwise be a wild global read
+  TORCH_CHECK(bag_idx.min().item<int64_t>() >= 0 &&
+                  bag_idx.max().item<int64_t>() < N,
+              "bag_idx holds a row outside [0, N)");
+  TORCH_CHECK(feat_sub.min().item<int32_t>() >= 0 &&
+                  feat_sub.max().item<int32_t>() < s.d,
+              "feat_sub holds a feature outside [0, d)");
+  return s;
+}
+
+// static LDS of the large build kernels (BlockPartials), rounded up
+constexpr size_t kLargeBuildStaticLds = 1024;
+
+}  // namespace
+
+std::vector<torch::Tensor> build_forest_large(
+    torch::Tensor X, torch::Tensor bag_idx, torch::Tensor feat_sub,
+    int64_t seed, int64_t tree_id_offset, torch::Tensor leaf_lut,
+    int64_t max_nodes, int64_t height_limit, int64_t threads) {
+  const LargeBuildShape s =
+      check_large_build(X, bag_idx, feat_sub, leaf_lut, tree_id_offset,
+                        max_nodes, height_limit, 1, false, threads);
+  const size_t lds = align16(4 * s.k) + (height_limit + 8) * 16;
+  TORCH_CHECK(lds + kLargeBuildStaticLds <= kMaxLds,
+              "build LDS request too large");
+
+  auto opts = bag_idx.options().dtype(torch::kInt32);
+  auto fopts = bag_idx.options().dtype(torch::kFloat32);
+  auto scratch = torch::empty({s.T, 2, s.n}, opts);
+  auto feat = torch::empty({s.T, max_nodes}, opts);
+  auto value = torch::empty({s.T, max_nodes}, fopts);
+  auto right = torch::full({s.T, max_nodes}, -1, opts);
+  auto count = torch::empty({s.T, max_nodes}, opts);
+  auto ncount = torch::empty({s.T}, opts);
+  auto depth = torch::zeros({s.T, max_nodes}, opts);
+
+  ifa::launch_build_forest_large(
+      row_dtype(X), X.data_ptr(), s.xl.rs, s.xl.cs,
+      bag_idx.data_ptr<int64_t>(), (uint32_t*)scratch.data_ptr<int32_t>(),
+      feat_sub.data_ptr<int32_t>(), feat.data_ptr<int32_t>(),
+      value.data_ptr<float>(), right.data_ptr<int32_t>(),
+      count.data_ptr<int32_t>(), ncount.data_ptr<int32_t>(),
+      depth.data_ptr<int32_t>(), leaf_lut.data_ptr<float>(), (uint64_t)seed,
+      (int32_t)tree_id_offset, (int32_t)s.T, (int32_t)s.n, (int32_t)s.k,
+      (int32_t)max_nodes, (int32_t)height_limit, (int)threads, lds,
+      current_stream());
+  return {feat, value, right, count, ncount, depth};
+}
+
+std::vector<torch::Tensor> build_extended_forest_large(
+    torch::Tensor X, torch::Tensor bag_idx, torch::Tensor feat_sub,
+    int64_t seed, int64_t tree_id_offset, torch::Tensor leaf_lut, int64_t nnz,
+    int64_t max_nodes, int64_t height_limit, int64_t threads) {
+  const LargeBuildShape s =
+      check_large_build(X, bag_idx, feat_sub, leaf_lut, tree_id_offset,
+                        max_nodes, height_limit, nnz, true, threads);
+  // coff[nnz] i64 | avail[k] i32 | coords[nnz] i32 | wf[nnz] f32 | stack
+  const size_t lds =
+      align16(8 * nnz + 4 * s.k + 8 * nnz) + (height_limit + 8) * 16 + 16;
+  TORCH_CHECK(lds + kLargeBuildStaticLds <= kMaxLds,
+              "build LDS request too large");
+
+  auto opts = bag_idx.options().dtype(torch::kInt32);
+  auto fopts = bag_idx.options().dtype(torch::kFloat32);
+  auto scratch = torch::empty({s.T, 2, s.n}, opts);
+  auto feat = torch::empty({s.T, max_nodes}, opts);
+  auto value = torch::empty({s.T, max_nodes}, fopts);
+  auto right = torch::full({s.T, max_nodes}, -1, opts);
+  auto count = torch::empty({s.T, max_nodes}, opts);
+  auto ncount = torch::empty({s.T}, opts);
+  auto hidx = torch::zeros({s.T, max_nodes, nnz}, opts);
+  auto hw = torch::zeros({s.T, max_nodes, nnz}, fopts);
+  auto off64 = torch::zeros({s.T, max_nodes},
+                            bag_idx.options().dtype(torch::kFloat64));
+  auto depth = torch::zeros({s.T, max_nodes}, opts);
+
+  ifa::launch_build_extended_forest_large(
+      row_dtype(X), X.data_ptr(), s.xl.rs, s.xl.cs,
+      bag_idx.data_ptr<int64_t>(), (uint32_t*)scratch.data_ptr<int32_t>(),
+      feat_sub.data_ptr<int32_t>(), feat.data_ptr<int32_t>(),
+      value.data_ptr<float>(), right.data_ptr<int32_t>(),
+      count.data_ptr<int32_t>(), ncount.data_ptr<int32_t>(),
+      hidx.data_ptr<int32_t>(), hw.data_ptr<float>(),
+      off64.data_ptr<double>(), depth.data_ptr<int32_t>(),
+      leaf_lut.data_ptr<float>(), (uint64_t)seed, (int32_t)tree_id_offset,
+      (int32_t)s.T, (int32_t)s.n, (int32_t)s.k, (int32_t)nnz,
+      (int32_t)max_nodes, (int32_t)height_limit, (int)threads, lds,
+      current_stream());
   return {feat, value, right, count, ncount, hidx, hw, off64, depth};
 }
 
@@ -1216,6 +1397,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("build_forest", &build_forest, "build standard iTrees (K1/K2/K11)");
   m.def("build_extended_forest", &build_extended_forest,
         "build extended iTrees (K3-K5)");
+  m.def("build_forest_large", &build_forest_large,
+        "build standard iTrees over bags of any size, rows read in place",
+        py::arg("X"), py::arg("bag_idx"), py::arg("feat_sub"), py::arg("seed"),
+        py::arg("tree_id_offset"), py::arg("leaf_lut"), py::arg("max_nodes"),
+        py::arg("height_limit"), py::arg("threads") = 256);
+  m.def("build_extended_forest_large", &build_extended_forest_large,
+        "build extended iTrees over bags of any size, rows read in place",
+        py::arg("X"), py::arg("bag_idx"), py::arg("feat_sub"), py::arg("seed"),
+        py::arg("tree_id_offset"), py::arg("leaf_lut"), py::arg("nnz"),
+        py::arg("max_nodes"), py::arg("height_limit"),
+        py::arg("threads") = 256);
   m.def("v4_level_order", &v4_level_order,
         "re-lay pre-order v4 node records in level order for score_forest");
   m.def("v4_heap_order", &v4_heap_order,

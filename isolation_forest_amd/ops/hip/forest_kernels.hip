@@ -10,6 +10,12 @@
 //    depths for the scoring pack.
 //  * build_extended_forest_kernel — K3-K5 (EIF Gaussian hyperplane draw,
 //    L2 normalize, per-coordinate min/max + offset, dot-product partition).
+//  * build_forest_large_kernel /
+//    build_extended_forest_large_kernel — the same two builds for bags of
+//    more than 16384 rows: one multi-wave block per tree, 32-bit row ids in
+//    a global ping-pong scratch, rows read in place from X (any admitted
+//    dtype and layout), block-wide min/max and stable partition. Bitwise the
+//    same forests.
 //  * score_forest_v4              — K6/K8 standard scoring: integer-KEY
 //    compares (rows staged in LDS as order-preserving u16/u32 keys,
 //    per-node integer thresholds), depth folded into f32 leaf values,
@@ -495,6 +501,480 @@ __global__ void __launch_bounds__(WAVE) build_extended_forest_kernel(
     sp += 2;
   }
   if (lane == 0) out_ncount[t] = next_id;
+}
+
+// ---------------------------------------------------------------------------
+// large-bag build (n > 16384): one block of several waves per tree
+//
+// The two kernels above keep a bag's row positions in LDS as 16-bit values
+// and read a pre-gathered f32 copy of every bag; neither survives big bags.
+// Their siblings here keep the working set in global memory:
+//   * scratch[t][2][n] (uint32) holds the tree's row permutation. It stores
+//     the GLOBAL ROW IDS of X (bag_idx[t][slot], narrowed to 32 bits; the
+//     bindings check N <= 2^32), not bag slots, so a cell is one dependent
+//     load away (scratch -> X) instead of two. Rows are read in place from X
+//     through load_feat<XT> and the two element strides.
+//   * the two halves ping-pong: a segment at height h lives in half h & 1,
+//     its partition writes the children into half (h + 1) & 1. Pending stack
+//     entries cover ranges disjoint from the current one, so nothing live is
+//     overwritten and no copy-back pass exists.
+//   * stack entries, node ids and segment bounds are 32-bit.
+// The pre-order DFS stays serial per tree (Philox draws are keyed by the
+// pre-order node id); the block parallelises inside a node. Min/max: wave
+// shuffle, then per-wave partials combined through LDS (fminf/fmaxf give the
+// same bits in any order). Partition: every wave owns a contiguous slice of
+// the segment, counts its left-goers, an exclusive prefix over the waves'
+// counts gives each slice its left and right base, then the slice is placed
+// with the ballot/popcount ranks of the one-wave kernels. A stable partition
+// has one result, so the forest is bitwise the one-wave kernels' (and
+// cpu_engine's). Segments of at most one wave skip the LDS combine: every
+// wave computes the whole segment itself and wave 0 alone stores.
+// Every branch around a barrier is block-uniform (m, height, found, acc).
+// ---------------------------------------------------------------------------
+
+#define BL_MAX_THREADS 512
+#define BL_MAX_WAVES (BL_MAX_THREADS / WAVE)
+#define BL_G 8  // coordinates per min/max pass of the extended build
+
+struct SegEntryL {
+  uint32_t start, end;
+  int32_t height;
+  int32_t patch;  // node whose `right` points at the node this entry emits
+};
+
+// Per-wave partials, double-buffered: each block-wide combine writes half
+// `pp`, meets at ONE barrier, reads, and flips pp. A half is rewritten two
+// combines later at the earliest, i.e. after a barrier every thread reached
+// only once it had finished reading it.
+struct BlockPartials {
+  float lo[2][BL_MAX_WAVES][BL_G];
+  float hi[2][BL_MAX_WAVES][BL_G];
+  uint32_t cnt[2][BL_MAX_WAVES];
+};
+
+// min/max of G columns (element offsets coff[g] = column * cs) over the rows
+// src[start, end), block-wide; every thread returns all G results
+template <typename XT, int G>
+__device__ __forceinline__ void seg_minmax(
+    const XT* __restrict__ X, int64_t rs, const int64_t (&coff)[G],
+    const uint32_t* __restrict__ src, uint32_t start, uint32_t end,
+    BlockPartials& bp, int& pp, float (&lo)[G], float (&hi)[G]) {
+  const uint32_t tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+  const uint32_t nw = blockDim.x / WAVE;
+  const bool small = end - start <= WAVE;  // block-uniform
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    lo[g] = __builtin_inff();
+    hi[g] = -__builtin_inff();
+  }
+  const uint32_t step = small ? WAVE : blockDim.x;
+#pragma unroll 4
+  for (uint32_t i = start + (small ? lane : tid); i < end; i += step) {
+    const int64_t ro = (int64_t)src[i] * rs;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const float v = load_feat<XT>(X, ro + coff[g]);
+      lo[g] = fminf(lo[g], v);
+      hi[g] = fmaxf(hi[g], v);
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    lo[g] = wave_reduce_min(lo[g]);
+    hi[g] = wave_reduce_max(hi[g]);
+  }
+  if (!small) {
+    if (lane == 0) {
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        bp.lo[pp][wave][g] = lo[g];
+        bp.hi[pp][wave][g] = hi[g];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      float a = bp.lo[pp][0][g], b = bp.hi[pp][0][g];
+      for (uint32_t w = 1; w < nw; ++w) {
+        a = fminf(a, bp.lo[pp][w][g]);
+        b = fmaxf(b, bp.hi[pp][w][g]);
+      }
+      lo[g] = a;
+      hi[g] = b;
+    }
+    pp ^= 1;
+  }
+}
+
+// Stable partition of the rows src[start, end) by pred(row) (true = left)
+// into dst[start, end); returns the left count to every thread. The caller
+// puts a barrier after it before anyone reads dst.
+template <typename Pred>
+__device__ __forceinline__ uint32_t seg_partition(
+    const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
+    uint32_t start, uint32_t end, BlockPartials& bp, int& pp, Pred pred) {
+  const uint32_t tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+  const uint32_t nw = blockDim.x / WAVE;
+  const uint32_t m = end - start;
+  if (m <= WAVE) {  // block-uniform; no barrier inside
+    const uint32_t i = start + lane;
+    const bool valid = i < end;
+    const uint32_t my = valid ? src[i] : 0u;
+    const bool p = valid && pred(my);
+    const uint64_t maskL = __ballot(p);
+    const uint64_t maskR = __ballot(valid && !p);
+    const uint32_t cntL = (uint32_t)__popcll(maskL);
+    if (wave == 0) {
+      if (p)
+        dst[start + __popcll(maskL & LANE_MASK_LT(lane))] = my;
+      else if (valid)
+        dst[start + cntL + __popcll(maskR & LANE_MASK_LT(lane))] = my;
+    }
+    return cntL;
+  }
+  // contiguous slice per wave, a whole number of 64-row steps
+  const uint32_t chunk = ((m + nw - 1) / nw + (WAVE - 1)) & ~(uint32_t)(WAVE - 1);
+  const uint32_t wo = min(wave * chunk, m);
+  const uint32_t ws = start + wo;
+  const uint32_t we = start + min(wo + chunk, m);
+  uint32_t c = 0;
+#pragma unroll 4
+  for (uint32_t i = ws + lane; i < we; i += WAVE) c += pred(src[i]) ? 1u : 0u;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, WAVE);
+  if (lane == 0) bp.cnt[pp][wave] = c;
+  __syncthreads();
+  uint32_t cntL = 0, leftBase = 0;
+  for (uint32_t w = 0; w < nw; ++w) {
+    const uint32_t v = bp.cnt[pp][w];
+    if (w < wave) leftBase += v;
+    cntL += v;
+  }
+  pp ^= 1;
+  uint32_t posL = start + leftBase;
+  uint32_t posR = start + cntL + (wo - leftBase);
+  for (uint32_t base = ws; base < we; base += 4 * WAVE) {
+    uint32_t my[4];
+    bool valid[4], p[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const uint32_t i = base + u * WAVE + lane;
+      valid[u] = i < we;
+      my[u] = valid[u] ? src[i] : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) p[u] = valid[u] && pred(my[u]);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const uint64_t maskL = __ballot(p[u]);
+      const uint64_t maskR = __ballot(valid[u] && !p[u]);
+      if (p[u])
+        dst[posL + __popcll(maskL & LANE_MASK_LT(lane))] = my[u];
+      else if (valid[u])
+        dst[posR + __popcll(maskR & LANE_MASK_LT(lane))] = my[u];
+      posL += (uint32_t)__popcll(maskL);
+      posR += (uint32_t)__popcll(maskR);
+    }
+  }
+  return cntL;
+}
+
+template <typename XT>
+__global__ void __launch_bounds__(BL_MAX_THREADS) build_forest_large_kernel(
+    const XT* __restrict__ X, int64_t rs, int64_t cs,
+    const int64_t* __restrict__ bag_idx,   // [T][n] rows of X
+    uint32_t* __restrict__ scratch,        // [T][2][n]
+    const int32_t* __restrict__ feat_sub,  // [T][k] sorted global feature ids
+    int32_t* __restrict__ out_feat,        // [T][max_nodes]
+    float* __restrict__ out_value,         // [T][max_nodes]
+    int32_t* __restrict__ out_right,       // [T][max_nodes], pre-filled -1
+    int32_t* __restrict__ out_count,       // [T][max_nodes] (leaf counts; -1)
+    int32_t* __restrict__ out_ncount,      // [T]
+    int32_t* __restrict__ out_depth,       // [T][max_nodes]
+    const float* __restrict__ leaf_lut,    // [n+1]: c(m) float32
+    uint64_t seed, int32_t tree_id_offset, int32_t n, int32_t k,
+    int32_t max_nodes, int32_t height_limit) {
+  __shared__ BlockPartials bp;
+  const int t = blockIdx.x;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t gtree = (uint32_t)(t + tree_id_offset);
+
+  int32_t* avail = (int32_t*)smem;  // [k]
+  SegEntryL* stack = (SegEntryL*)(((uintptr_t)(avail + k) + 15) & ~15ull);
+
+  uint32_t* buf0 = scratch + (int64_t)t * 2 * n;
+  uint32_t* buf1 = buf0 + n;
+  const int64_t* bagp = bag_idx + (int64_t)t * n;
+  int32_t* feat = out_feat + (int64_t)t * max_nodes;
+  float* value = out_value + (int64_t)t * max_nodes;
+  int32_t* right = out_right + (int64_t)t * max_nodes;
+  int32_t* count = out_count + (int64_t)t * max_nodes;
+  int32_t* depth = out_depth + (int64_t)t * max_nodes;
+  const int32_t* features = feat_sub + (int64_t)t * k;
+
+  for (uint32_t i = tid; i < (uint32_t)n; i += blockDim.x)
+    buf0[i] = (uint32_t)bagp[i];
+  if (tid == 0) stack[0] = SegEntryL{0u, (uint32_t)n, 0, -1};
+  __syncthreads();
+
+  int sp = 1, pp = 0;
+  int32_t next_id = 0;
+  while (sp > 0) {
+    const SegEntryL e = stack[--sp];
+    const int32_t node = next_id++;
+    if (tid == 0) {
+      if (e.patch >= 0) right[e.patch] = node;
+      depth[node] = e.height;
+    }
+    const uint32_t start = e.start, end = e.end, m = end - start;
+
+    if (m <= 1 || e.height >= height_limit) {
+      if (tid == 0) {
+        feat[node] = -1;
+        value[node] = leaf_lut[m];
+        count[node] = (int32_t)m;
+      }
+      continue;
+    }
+    const uint32_t* src = (e.height & 1) ? buf1 : buf0;
+    uint32_t* dst = (e.height & 1) ? buf0 : buf1;
+
+    // ---- feature selection with constant-feature retry (K1 + K11) ----
+    for (uint32_t j = tid; j < (uint32_t)k; j += blockDim.x)
+      avail[j] = features[j];
+    __syncthreads();
+    int found = -1;
+    float fmin = 0.f, fmax = 0.f;
+    for (int j = 0; j < k; ++j) {
+      uint32_t r = rng_below(seed, P_FEATSEL, gtree, (uint32_t)node,
+                             (uint32_t)(k - j), (uint32_t)j);
+      int tsel = j + (int)r;
+      if (tid == 0) {
+        int32_t a = avail[j];
+        avail[j] = avail[tsel];
+        avail[tsel] = a;
+      }
+      __syncthreads();
+      const int f = avail[j];
+      const int64_t coff[1] = {(int64_t)f * cs};
+      float lo[1], hi[1];
+      seg_minmax<XT, 1>(X, rs, coff, src, start, end, bp, pp, lo, hi);
+      if (lo[0] < hi[0]) {
+        found = f;
+        fmin = lo[0];
+        fmax = hi[0];
+        break;
+      }
+    }
+    if (found < 0) {
+      if (tid == 0) {
+        feat[node] = -1;
+        value[node] = leaf_lut[m];
+        count[node] = (int32_t)m;
+      }
+      // the last avail[j] reads end here, before the next node refills it
+      __syncthreads();
+      continue;
+    }
+
+    const double u = rng_uniform(seed, P_SPLIT, gtree, (uint32_t)node);
+    const float s32 = split_value32(fmin, fmax, u);
+
+    // ---- stable partition (K2) ----
+    const int64_t foff = (int64_t)found * cs;
+    const uint32_t cntL = seg_partition(
+        src, dst, start, end, bp, pp, [&](uint32_t row) {
+          return load_feat<XT>(X, (int64_t)row * rs + foff) < s32;
+        });
+
+    if (tid == 0) {
+      feat[node] = found;
+      value[node] = s32;
+      count[node] = -1;
+      // pre-order: push right, then left (left pops first = node+1)
+      stack[sp] = SegEntryL{start + cntL, end, e.height + 1, node};
+      stack[sp + 1] = SegEntryL{start, start + cntL, e.height + 1, -1};
+    }
+    __syncthreads();  // dst and the stack, for every wave
+    sp += 2;
+  }
+  if (tid == 0) out_ncount[t] = next_id;
+}
+
+template <typename XT>
+__global__ void __launch_bounds__(BL_MAX_THREADS)
+build_extended_forest_large_kernel(
+    const XT* __restrict__ X, int64_t rs, int64_t cs,
+    const int64_t* __restrict__ bag_idx, uint32_t* __restrict__ scratch,
+    const int32_t* __restrict__ feat_sub, int32_t* __restrict__ out_feat,
+    float* __restrict__ out_value, int32_t* __restrict__ out_right,
+    int32_t* __restrict__ out_count, int32_t* __restrict__ out_ncount,
+    int32_t* __restrict__ out_hidx,    // [T][max_nodes][nnz]
+    float* __restrict__ out_hw,        // [T][max_nodes][nnz]
+    double* __restrict__ out_off64,    // [T][max_nodes]
+    int32_t* __restrict__ out_depth,   // [T][max_nodes]
+    const float* __restrict__ leaf_lut, uint64_t seed, int32_t tree_id_offset,
+    int32_t n, int32_t k, int32_t nnz, int32_t max_nodes,
+    int32_t height_limit) {
+  __shared__ BlockPartials bp;
+  const int t = blockIdx.x;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t gtree = (uint32_t)(t + tree_id_offset);
+
+  int64_t* coff = (int64_t*)smem;           // [nnz] coords[j] * cs
+  int32_t* avail = (int32_t*)(coff + nnz);  // [k]
+  int32_t* coords = avail + k;              // [nnz]
+  float* wf = (float*)(coords + nnz);       // [nnz]
+  SegEntryL* stack = (SegEntryL*)(((uintptr_t)(wf + nnz) + 15) & ~15ull);
+
+  uint32_t* buf0 = scratch + (int64_t)t * 2 * n;
+  uint32_t* buf1 = buf0 + n;
+  const int64_t* bagp = bag_idx + (int64_t)t * n;
+  int32_t* feat = out_feat + (int64_t)t * max_nodes;
+  float* value = out_value + (int64_t)t * max_nodes;
+  int32_t* right = out_right + (int64_t)t * max_nodes;
+  int32_t* count = out_count + (int64_t)t * max_nodes;
+  int32_t* hidx = out_hidx + (int64_t)t * max_nodes * nnz;
+  float* hw = out_hw + (int64_t)t * max_nodes * nnz;
+  double* off64p = out_off64 + (int64_t)t * max_nodes;
+  int32_t* depth = out_depth + (int64_t)t * max_nodes;
+  const int32_t* features = feat_sub + (int64_t)t * k;
+
+  for (uint32_t i = tid; i < (uint32_t)n; i += blockDim.x)
+    buf0[i] = (uint32_t)bagp[i];
+  if (tid == 0) stack[0] = SegEntryL{0u, (uint32_t)n, 0, -1};
+  __syncthreads();
+
+  int sp = 1, pp = 0;
+  int32_t next_id = 0;
+  while (sp > 0) {
+    const SegEntryL e = stack[--sp];
+    const int32_t node = next_id++;
+    if (tid == 0) {
+      if (e.patch >= 0) right[e.patch] = node;
+      depth[node] = e.height;
+    }
+    const uint32_t start = e.start, end = e.end, m = end - start;
+
+    if (m <= 1 || e.height >= height_limit) {
+      if (tid == 0) {
+        feat[node] = -1;
+        value[node] = leaf_lut[m];
+        count[node] = (int32_t)m;
+      }
+      continue;
+    }
+    const uint32_t* src = (e.height & 1) ? buf1 : buf0;
+    uint32_t* dst = (e.height & 1) ? buf0 : buf1;
+
+    // ---- coordinate subset: Fisher-Yates over the tree's subspace ----
+    for (uint32_t j = tid; j < (uint32_t)k; j += blockDim.x)
+      avail[j] = features[j];
+    __syncthreads();
+    // thread 0 alone draws, swaps and sorts (insertion sort, ascending);
+    // the others meet it at the barrier after the Gaussian draws
+    if (tid == 0) {
+      for (int j = 0; j < nnz; ++j) {
+        uint32_t r = rng_below(seed, P_EIF_COORD, gtree, (uint32_t)node,
+                               (uint32_t)(k - j), (uint32_t)j);
+        int tsel = j + (int)r;
+        int32_t a = avail[j];
+        avail[j] = avail[tsel];
+        avail[tsel] = a;
+      }
+      for (int a = 1; a < nnz; ++a) {
+        int32_t key = avail[a];
+        int b = a - 1;
+        while (b >= 0 && avail[b] > key) {
+          avail[b + 1] = avail[b];
+          --b;
+        }
+        avail[b + 1] = key;
+      }
+      for (int j = 0; j < nnz; ++j) {
+        coords[j] = avail[j];
+        coff[j] = (int64_t)avail[j] * cs;
+      }
+    }
+
+    // ---- Gaussian weights per sorted slot (det Box-Muller), parallel ----
+    const uint32_t base = (uint32_t)node * 4096u;
+    for (uint32_t j = tid; j < (uint32_t)nnz; j += blockDim.x) {
+      double u1, u2;
+      rng_uniform2(seed, P_EIF_NORMAL, gtree, base + j, &u1, &u2);
+      wf[j] = (float)det_gaussian(u1, u2);
+    }
+    __syncthreads();
+    // sequential float32 norm (order == CPU oracle)
+    float acc = 0.f;
+    for (int j = 0; j < nnz; ++j) acc = __fadd_rn(acc, __fmul_rn(wf[j], wf[j]));
+    // every wave has summed the raw weights before any is normalised, and
+    // before the next node's draws on the zero-norm path
+    __syncthreads();
+    if (acc <= 0.f) {  // theoretical zero-norm leaf
+      if (tid == 0) {
+        feat[node] = -1;
+        value[node] = leaf_lut[m];
+        count[node] = (int32_t)m;
+      }
+      continue;
+    }
+    // sqrt/divide through double, as build_extended_forest_kernel
+    const float norm = (float)sqrt((double)acc);
+    for (uint32_t j = tid; j < (uint32_t)nnz; j += blockDim.x)
+      wf[j] = (float)((double)wf[j] / (double)norm);
+    __syncthreads();
+
+    // ---- intercepts per sorted coordinate + offset (float64, j order) ----
+    // BL_G coordinates share one pass over the segment
+    double off64 = 0.0;
+    for (int j0 = 0; j0 < nnz; j0 += BL_G) {
+      int64_t co[BL_G];
+#pragma unroll
+      for (int g = 0; g < BL_G; ++g) co[g] = coff[min(j0 + g, nnz - 1)];
+      float lo[BL_G], hi[BL_G];
+      seg_minmax<XT, BL_G>(X, rs, co, src, start, end, bp, pp, lo, hi);
+#pragma unroll
+      for (int g = 0; g < BL_G; ++g) {
+        const int j = j0 + g;
+        if (j < nnz) {
+          const double u =
+              rng_uniform(seed, P_EIF_INTERCEPT, gtree, base + (uint32_t)j);
+          const double intercept =
+              (double)lo[g] + u * ((double)hi[g] - (double)lo[g]);
+          off64 += (double)wf[j] * intercept;
+        }
+      }
+    }
+    const float off32 = (float)off64;
+
+    // ---- partition by hyperplane dot (no retry; empty sides allowed) ----
+    const uint32_t cntL = seg_partition(
+        src, dst, start, end, bp, pp, [&](uint32_t row) {
+          const int64_t ro = (int64_t)row * rs;
+          float dot = 0.f;
+          for (int j = 0; j < nnz; ++j)
+            dot = __fadd_rn(dot,
+                            __fmul_rn(wf[j], load_feat<XT>(X, ro + coff[j])));
+          return dot < off32;
+        });
+
+    for (uint32_t j = tid; j < (uint32_t)nnz; j += blockDim.x) {
+      hidx[(int64_t)node * nnz + j] = coords[j];
+      hw[(int64_t)node * nnz + j] = wf[j];
+    }
+    if (tid == 0) {
+      feat[node] = nnz;
+      value[node] = off32;
+      off64p[node] = off64;
+      count[node] = -1;
+      stack[sp] = SegEntryL{start + cntL, end, e.height + 1, node};
+      stack[sp + 1] = SegEntryL{start, start + cntL, e.height + 1, -1};
+    }
+    __syncthreads();  // dst, the stack, and the last coords/wf reads
+    sp += 2;
+  }
+  if (tid == 0) out_ncount[t] = next_id;
 }
 
 // ---------------------------------------------------------------------------
@@ -2353,6 +2833,66 @@ void launch_build_extended_forest(const float* bags, const int32_t* feat_sub,
                      hidx, hw, off64, depth, leaf_lut, seed, tree_id_offset,
                      n, d, k, nnz, max_nodes, height_limit);
 }
+
+// tools/native/ifa_score only scores: it is built with IFA_NO_LARGE_BUILD and
+// leaves these six instantiations out (binary size cap, as above the heap
+// route below).
+#ifndef IFA_NO_LARGE_BUILD
+// threads: a multiple of 64, at most BL_MAX_THREADS
+void launch_build_forest_large(RowDtype dt, const void* X, int64_t rs,
+                               int64_t cs, const int64_t* bag_idx,
+                               uint32_t* scratch, const int32_t* feat_sub,
+                               int32_t* feat, float* value, int32_t* right,
+                               int32_t* count, int32_t* ncount, int32_t* depth,
+                               const float* leaf_lut, uint64_t seed,
+                               int32_t tree_id_offset, int32_t T, int32_t n,
+                               int32_t k, int32_t max_nodes,
+                               int32_t height_limit, int threads, size_t lds,
+                               hipStream_t stream) {
+#define BL_LAUNCH(XT)                                                         \
+  do {                                                                        \
+    raise_lds((const void*)build_forest_large_kernel<XT>, lds);               \
+    hipLaunchKernelGGL(build_forest_large_kernel<XT>, dim3(T), dim3(threads), \
+                       lds, stream, (const XT*)X, rs, cs, bag_idx, scratch,   \
+                       feat_sub, feat, value, right, count, ncount, depth,    \
+                       leaf_lut, seed, tree_id_offset, n, k, max_nodes,       \
+                       height_limit);                                         \
+  } while (0)
+  if (dt == ROW_BF16)
+    BL_LAUNCH(uint16_t);
+  else if (dt == ROW_F16)
+    BL_LAUNCH(f16_t);
+  else
+    BL_LAUNCH(float);
+#undef BL_LAUNCH
+}
+
+void launch_build_extended_forest_large(
+    RowDtype dt, const void* X, int64_t rs, int64_t cs, const int64_t* bag_idx,
+    uint32_t* scratch, const int32_t* feat_sub, int32_t* feat, float* value,
+    int32_t* right, int32_t* count, int32_t* ncount, int32_t* hidx, float* hw,
+    double* off64, int32_t* depth, const float* leaf_lut, uint64_t seed,
+    int32_t tree_id_offset, int32_t T, int32_t n, int32_t k, int32_t nnz,
+    int32_t max_nodes, int32_t height_limit, int threads, size_t lds,
+    hipStream_t stream) {
+#define BL_LAUNCH(XT)                                                         \
+  do {                                                                        \
+    raise_lds((const void*)build_extended_forest_large_kernel<XT>, lds);      \
+    hipLaunchKernelGGL(build_extended_forest_large_kernel<XT>, dim3(T),       \
+                       dim3(threads), lds, stream, (const XT*)X, rs, cs,      \
+                       bag_idx, scratch, feat_sub, feat, value, right, count, \
+                       ncount, hidx, hw, off64, depth, leaf_lut, seed,        \
+                       tree_id_offset, n, k, nnz, max_nodes, height_limit);   \
+  } while (0)
+  if (dt == ROW_BF16)
+    BL_LAUNCH(uint16_t);
+  else if (dt == ROW_F16)
+    BL_LAUNCH(f16_t);
+  else
+    BL_LAUNCH(float);
+#undef BL_LAUNCH
+}
+#endif  // IFA_NO_LARGE_BUILD
 
 void launch_v4_level_order(const void* nodes, const int32_t* ncount,
                            void* out, int32_t Tpad, int32_t max_nodes,
