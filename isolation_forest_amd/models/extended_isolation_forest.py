@@ -27,34 +27,29 @@ class ExtendedIsolationForest(IsolationForest):
 
     def _build_local(self, X, rp, seed, t_lo, t_hi, n_local):
         T_local = t_hi - t_lo
-        bag_idx = cpu_engine.sample_bags(
-            n_local, T_local, rp.num_samples, seed,
-            self.params.get("bootstrap"), tree_id_offset=t_lo,
-        )
         feat_sub = cpu_engine.feature_subsets(
             rp.total_features, rp.num_features, T_local, seed, tree_id_offset=t_lo
         )
-        if X.is_cuda and rp.num_samples <= 16384:
-            from ..ops import gpu_engine
-
-            return gpu_engine.build_extended_forest(
-                X, bag_idx, feat_sub, seed, rp, tree_id_offset=t_lo
-            )
         if X.is_cuda:
             import logging
 
             from ..ops import gpu_engine
 
-            if gpu_engine.large_build_fits(X, rp.num_samples):
-                return gpu_engine.build_extended_forest_large(
-                    X, bag_idx, feat_sub, seed, rp, tree_id_offset=t_lo
-                )
+            large = rp.num_samples > 16384
+            if not large or gpu_engine.large_build_fits(X, rp.num_samples):
+                bag_idx, kw = self._gpu_build_inputs(
+                    X, rp, seed, t_lo, t_hi, n_local)
+                build = (gpu_engine.build_extended_forest_large if large
+                         else gpu_engine.build_extended_forest)
+                return build(X, bag_idx, feat_sub, seed, rp,
+                             tree_id_offset=t_lo, **kw)
             logging.getLogger(__name__).warning(
                 "maxSamples %d over %d rows exceeds the GPU build's 32-bit "
                 "row ids; building trees on CPU (scoring stays on GPU)",
                 rp.num_samples, X.shape[0],
             )
             X = X.float().cpu()
+        bag_idx = self._host_bags(rp, seed, t_lo, t_hi, n_local)
         Xc = X.contiguous().float().numpy()
         return cpu_engine.build_extended_forest(
             Xc, bag_idx, feat_sub, seed, rp.num_samples, rp.num_features,

@@ -119,36 +119,55 @@ class IsolationForest:
     def _model_cls(self):
         return IsolationForestModel
 
-    def _build_local(self, X, rp, seed, t_lo, t_hi, n_local):
-        T_local = t_hi - t_lo
-        bag_idx = cpu_engine.sample_bags(
-            n_local, T_local, rp.num_samples, seed,
+    def _host_bags(self, rp, seed, t_lo, t_hi, n_local):
+        return cpu_engine.sample_bags(
+            n_local, t_hi - t_lo, rp.num_samples, seed,
             self.params.get("bootstrap"), tree_id_offset=t_lo,
         )
+
+    def _gpu_build_inputs(self, X, rp, seed, t_lo, t_hi, n_local):
+        """``(bag_idx, kwargs)`` for a GPU builder. With the device sampler
+        (gpu_engine.bag_device_enabled) the bags never touch the host: the
+        LDS builders get a device tensor, the large ones ``None`` and draw
+        each tree chunk themselves. Else the host sampler's matrix. Same
+        bags either way, bitwise."""
+        from ..ops import gpu_engine
+
+        n = rp.num_samples
+        bootstrap = self.params.get("bootstrap")
+        if not gpu_engine.bag_device_enabled(n_local, n):
+            return self._host_bags(rp, seed, t_lo, t_hi, n_local), {}
+        if n > 16384:
+            return None, {"bootstrap": bootstrap}
+        return gpu_engine.sample_bags_device(
+            n_local, t_hi - t_lo, n, seed, bootstrap, tree_id_offset=t_lo,
+            device=X.device), {}
+
+    def _build_local(self, X, rp, seed, t_lo, t_hi, n_local):
+        T_local = t_hi - t_lo
         feat_sub = cpu_engine.feature_subsets(
             rp.total_features, rp.num_features, T_local, seed, tree_id_offset=t_lo
         )
-        if X.is_cuda and rp.num_samples <= 16384:
-            from ..ops import gpu_engine
-
-            return gpu_engine.build_forest(
-                X, bag_idx, feat_sub, seed, rp, tree_id_offset=t_lo
-            )
         if X.is_cuda:
             from ..ops import gpu_engine
 
             # past the LDS kernels' 16384-row bags: the multi-wave builders,
             # which keep the row ids in global memory and read X in place
-            if gpu_engine.large_build_fits(X, rp.num_samples):
-                return gpu_engine.build_forest_large(
-                    X, bag_idx, feat_sub, seed, rp, tree_id_offset=t_lo
-                )
+            large = rp.num_samples > 16384
+            if not large or gpu_engine.large_build_fits(X, rp.num_samples):
+                bag_idx, kw = self._gpu_build_inputs(
+                    X, rp, seed, t_lo, t_hi, n_local)
+                build = (gpu_engine.build_forest_large if large
+                         else gpu_engine.build_forest)
+                return build(X, bag_idx, feat_sub, seed, rp,
+                             tree_id_offset=t_lo, **kw)
             logger.warning(
                 "maxSamples %d over %d rows exceeds the GPU build's 32-bit "
                 "row ids; building trees on CPU (scoring stays on GPU)",
                 rp.num_samples, X.shape[0],
             )
             X = X.float().cpu()
+        bag_idx = self._host_bags(rp, seed, t_lo, t_hi, n_local)
         Xc = X.contiguous().float().numpy()
         return cpu_engine.build_forest(
             Xc, bag_idx, feat_sub, seed, rp.num_samples, rp.num_features,

@@ -1,7 +1,8 @@
 """GPU engine orchestration: device builds and scoring via the HIP extension.
 
 The canonical forest lives in host numpy (core/forest.py) — it is small
-(MBs) next to the data (GBs-TBs). Bags/feature subsets are drawn host-side
+(MBs) next to the data (GBs-TBs). Feature subsets are drawn host-side and
+bags on the device (sample_bags_device, bitwise the host sampler's), all
 with the same Philox counters the kernels use, so a GPU-built forest is
 BIT-IDENTICAL to the CPU oracle's for the same seed (tests/test_gpu.py
 enforces this). Bags of up to 16384 rows build with the one-wave LDS kernels
@@ -93,14 +94,124 @@ def _mask_padding(feature, right, count, ncount, pad):
     return live
 
 
-def build_forest(X: torch.Tensor, bag_idx: np.ndarray, feat_sub: np.ndarray,
+# ---------------------------------------------------------------------------
+# on-device bag sampling (ops/hip/bag_kernels.hip, docs/DESIGN.md §2c)
+# ---------------------------------------------------------------------------
+
+# Largest bag the one-block-per-tree LDS sampler takes: its hash table of
+# 8 bytes * (next power of two >= 2n) is 128 KB there (kBagLdsMaxSamples in
+# bindings.cpp, which checks it). Larger bags use the global-table kernels.
+BAG_LDS_MAX_SAMPLES = 8192
+
+
+def bag_device_fits(total_rows: int, n: int) -> bool:
+    """Whether ``sample_bags_device`` takes bags of ``n`` out of
+    ``total_rows`` rows: draws are 32-bit and the all-ones word marks an empty
+    table entry, so ``total_rows <= 2^32 - 1``; slot ids as in the large
+    builders, ``n <= 2^30``."""
+    return 1 <= int(total_rows) <= (1 << 32) - 1 and int(n) <= 1 << 30
+
+
+def bag_device_enabled(total_rows: int, n: int) -> bool:
+    """The estimators' switch: the device sampler unless ``IFA_BAG_DEVICE=0``
+    (A/B runs, escape hatch) or the shape does not fit it."""
+    return (os.environ.get("IFA_BAG_DEVICE", "1") != "0"
+            and bag_device_fits(total_rows, n))
+
+
+def _bag_table_cap(n: int) -> int:
+    cap = 2
+    while cap < 2 * n:
+        cap <<= 1
+    return cap
+
+
+def _bag_sampler_bytes(total_rows: int, n: int, bootstrap: bool) -> int:
+    """Device bytes per tree the sampler allocates next to its output: the
+    global route's table and loser flags, or the dense regime's key matrix
+    with torch.sort's outputs and workspace (4 int64 per row)."""
+    if bootstrap or n <= 0:
+        return 0
+    if 2 * n > total_rows:
+        return 32 * total_rows
+    if n <= BAG_LDS_MAX_SAMPLES:
+        return 0
+    return 8 * _bag_table_cap(n) + n
+
+
+def sample_bags_device(total_rows: int, num_trees: int, num_samples: int,
+                       seed: int, bootstrap: bool, tree_id_offset: int = 0,
+                       row_offset: int = 0, device="cuda") -> torch.Tensor:
+    """``cpu_engine.sample_bags`` drawn on the GPU: the same int64
+    ``[num_trees, num_samples]`` matrix, bitwise, as a tensor on ``device``
+    (what ``bag_gather`` and the large builders read). Routes: bootstrap (one
+    draw per slot); without replacement and ``2n <= N`` a per-tree hash table
+    from value to smallest slot, in LDS up to ``BAG_LDS_MAX_SAMPLES`` rows a
+    bag and in global memory above (one host sync per redraw round); ``2n >
+    N`` the oracle's permutation as a ``torch.sort`` of composite keys."""
+    ext = load_extension()
+    N, T, n = int(total_rows), int(num_trees), int(num_samples)
+    if not bootstrap and n > N:
+        raise ValueError("cannot sample more rows than the dataset holds")
+    if not bag_device_fits(N, n):
+        raise ValueError(
+            f"device bag sampling needs total_rows <= 2^32 - 1 and "
+            f"num_samples <= 2^30 (got {N}, {n})")
+    device = torch.device(device)
+    with torch.cuda.device(device):
+        out = torch.empty((T, n), dtype=torch.int64, device=device)
+        if T == 0 or n == 0:
+            return out
+        if bootstrap:
+            ext.bag_bootstrap(out, N, seed, tree_id_offset, row_offset)
+            return out
+        per_tree = _bag_sampler_bytes(N, n, False)
+        if 2 * n > N:
+            chunk = max(1, BUILD_LARGE_BUDGET_BYTES // per_tree)
+            for lo in range(0, T, chunk):
+                hi = min(T, lo + chunk)
+                keys = torch.empty((hi - lo, N), dtype=torch.int64,
+                                   device=device)
+                ext.bag_dense_keys(keys, seed, tree_id_offset + lo)
+                first = torch.sort(keys, dim=1).values[:, :n]
+                out[lo:hi] = (first & 0xFFFFFFFF) + row_offset
+                del keys, first
+            return out
+        if n <= BAG_LDS_MAX_SAMPLES:
+            v = os.environ.get("IFA_BAG_LDS_THREADS")
+            ext.bag_sample_lds(out, N, seed, tree_id_offset, row_offset,
+                               int(v) if v else 0)
+            return out
+        # grid.y carries the tree; the loser total is an int32
+        chunk = max(1, min(65535, (2 ** 31 - 1) // n,
+                           BUILD_LARGE_BUDGET_BYTES // per_tree))
+        for lo in range(0, T, chunk):
+            hi = min(T, lo + chunk)
+            ext.bag_sample_global(out[lo:hi], N, seed, tree_id_offset + lo,
+                                  row_offset)
+        return out
+
+
+def _bag_tensor(bag_idx, device) -> torch.Tensor:
+    """Bags as the kernels read them: an int64 device tensor as it is (no
+    copy crosses PCIe), a numpy matrix uploaded."""
+    if isinstance(bag_idx, torch.Tensor):
+        if bag_idx.dtype != torch.int64 or bag_idx.device != device:
+            raise ValueError(
+                f"bag_idx tensor must be int64 on {device}; got "
+                f"{bag_idx.dtype} on {bag_idx.device}")
+        return bag_idx.contiguous()
+    return torch.from_numpy(np.ascontiguousarray(bag_idx)).to(device)
+
+
+def build_forest(X: torch.Tensor, bag_idx, feat_sub: np.ndarray,
                  seed: int, rp, tree_id_offset: int = 0) -> Forest:
     ext = load_extension()
     device = X.device
     n = rp.num_samples
     height_limit = int(math.ceil(math.log2(max(n, 2))))
     max_nodes = 2 * n - 1
-    bag_t = torch.from_numpy(np.ascontiguousarray(bag_idx)).to(device)
+    bag_t = _bag_tensor(bag_idx, device)
     fs_t = torch.from_numpy(np.ascontiguousarray(feat_sub, dtype=np.int32)).to(device)
     bags = ext.bag_gather(_rows_in_place(X), bag_t)
     feat, value, right, count, ncount, depth = ext.build_forest(
@@ -138,7 +249,7 @@ def build_forest(X: torch.Tensor, bag_idx: np.ndarray, feat_sub: np.ndarray,
     return forest
 
 
-def build_extended_forest(X: torch.Tensor, bag_idx: np.ndarray,
+def build_extended_forest(X: torch.Tensor, bag_idx,
                           feat_sub: np.ndarray, seed: int, rp,
                           tree_id_offset: int = 0) -> ExtendedForest:
     ext = load_extension()
@@ -147,7 +258,7 @@ def build_extended_forest(X: torch.Tensor, bag_idx: np.ndarray,
     height_limit = int(math.ceil(math.log2(max(n, 2))))
     max_nodes = 2 ** (height_limit + 1) - 1
     nnz = min(rp.extension_level + 1, rp.num_features)
-    bag_t = torch.from_numpy(np.ascontiguousarray(bag_idx)).to(device)
+    bag_t = _bag_tensor(bag_idx, device)
     fs_t = torch.from_numpy(np.ascontiguousarray(feat_sub, dtype=np.int32)).to(device)
     bags = ext.bag_gather(_rows_in_place(X), bag_t)
     (feat, value, right, count, ncount, hidx, hw, off64,
@@ -229,10 +340,22 @@ def _large_threads() -> int:
     return int(v) if v else BUILD_LARGE_THREADS
 
 
-def build_forest_large(X: torch.Tensor, bag_idx: np.ndarray,
+def _large_chunk_bags(bag_idx, lo: int, hi: int, X: torch.Tensor, n: int,
+                      seed: int, bootstrap: bool, tree_id_offset: int):
+    """Trees ``lo:hi`` of the bags on X's device: a slice of ``bag_idx``, or
+    with ``bag_idx=None`` drawn there by global tree id, so that the whole
+    ``[T, n]`` index matrix never exists."""
+    if bag_idx is None:
+        return sample_bags_device(int(X.shape[0]), hi - lo, n, seed, bootstrap,
+                                  tree_id_offset=tree_id_offset + lo,
+                                  device=X.device)
+    return _bag_tensor(bag_idx[lo:hi], X.device)
+
+
+def build_forest_large(X: torch.Tensor, bag_idx,
                        feat_sub: np.ndarray, seed: int, rp,
                        tree_id_offset: int = 0, chunk_trees=None,
-                       return_depth: bool = False):
+                       return_depth: bool = False, bootstrap: bool = False):
     """``build_forest`` for bags of any size (the models use it above the
     LDS builders' 16384 rows): rows are read in place from ``X``, no f32
     ``[T, n, d]`` gather is made, and the trees are built ``chunk_trees`` at
@@ -240,17 +363,21 @@ def build_forest_large(X: torch.Tensor, bag_idx: np.ndarray,
     forest is bitwise ``cpu_engine.build_forest``'s. It carries no device
     tensors: forests this size score through the host-packed wide formats.
     ``return_depth=True`` returns ``(forest, depth)`` with the kernel's
-    per-node depths ``[T, max_nodes]``."""
+    per-node depths ``[T, max_nodes]``. ``bag_idx`` is a numpy matrix, an
+    int64 tensor on X's device, or ``None``: each chunk's bags are then drawn
+    on the device (``sample_bags_device`` with ``bootstrap``)."""
     ext = load_extension()
     device = X.device
     n = rp.num_samples
     height_limit = int(math.ceil(math.log2(max(n, 2))))
     max_nodes = 2 * n - 1
-    T = int(bag_idx.shape[0])
     Xr = _rows_in_place(X)
     lut = _leaf_lut(n, device)
     fs = np.ascontiguousarray(feat_sub, dtype=np.int32)
-    chunk = _large_chunk_trees(T, 16 * n + 28 * max_nodes, chunk_trees)
+    T = int(fs.shape[0] if bag_idx is None else bag_idx.shape[0])
+    drawn = (_bag_sampler_bytes(int(X.shape[0]), n, bootstrap)
+             if bag_idx is None else 0)
+    chunk = _large_chunk_trees(T, 16 * n + 28 * max_nodes + drawn, chunk_trees)
     f_np = np.empty((T, max_nodes), dtype=np.int32)
     v_np = np.empty((T, max_nodes), dtype=np.float32)
     r_np = np.empty((T, max_nodes), dtype=np.int32)
@@ -259,7 +386,8 @@ def build_forest_large(X: torch.Tensor, bag_idx: np.ndarray,
     d_np = np.empty((T, max_nodes), dtype=np.int32) if return_depth else None
     for lo in range(0, T, chunk):
         hi = min(T, lo + chunk)
-        bag_t = torch.from_numpy(np.ascontiguousarray(bag_idx[lo:hi])).to(device)
+        bag_t = _large_chunk_bags(bag_idx, lo, hi, X, n, seed, bootstrap,
+                                  tree_id_offset)
         fs_t = torch.from_numpy(fs[lo:hi]).to(device)
         feat, value, right, count, ncount, depth = ext.build_forest_large(
             Xr, bag_t, fs_t, seed, tree_id_offset + lo, lut, max_nodes,
@@ -290,10 +418,11 @@ def build_forest_large(X: torch.Tensor, bag_idx: np.ndarray,
     return (forest, d_np) if return_depth else forest
 
 
-def build_extended_forest_large(X: torch.Tensor, bag_idx: np.ndarray,
+def build_extended_forest_large(X: torch.Tensor, bag_idx,
                                 feat_sub: np.ndarray, seed: int, rp,
                                 tree_id_offset: int = 0, chunk_trees=None,
-                                return_depth: bool = False):
+                                return_depth: bool = False,
+                                bootstrap: bool = False):
     """``build_extended_forest`` for bags of any size; see
     ``build_forest_large``."""
     ext = load_extension()
@@ -302,12 +431,14 @@ def build_extended_forest_large(X: torch.Tensor, bag_idx: np.ndarray,
     height_limit = int(math.ceil(math.log2(max(n, 2))))
     max_nodes = 2 ** (height_limit + 1) - 1
     nnz = min(rp.extension_level + 1, rp.num_features)
-    T = int(bag_idx.shape[0])
     Xr = _rows_in_place(X)
     lut = _leaf_lut(n, device)
     fs = np.ascontiguousarray(feat_sub, dtype=np.int32)
+    T = int(fs.shape[0] if bag_idx is None else bag_idx.shape[0])
+    drawn = (_bag_sampler_bytes(int(X.shape[0]), n, bootstrap)
+             if bag_idx is None else 0)
     chunk = _large_chunk_trees(
-        T, 16 * n + (28 + 8 * nnz) * max_nodes, chunk_trees)
+        T, 16 * n + (28 + 8 * nnz) * max_nodes + drawn, chunk_trees)
     f_np = np.empty((T, max_nodes), dtype=np.int32)
     v_np = np.empty((T, max_nodes), dtype=np.float32)
     r_np = np.empty((T, max_nodes), dtype=np.int32)
@@ -319,7 +450,8 @@ def build_extended_forest_large(X: torch.Tensor, bag_idx: np.ndarray,
     d_np = np.empty((T, max_nodes), dtype=np.int32) if return_depth else None
     for lo in range(0, T, chunk):
         hi = min(T, lo + chunk)
-        bag_t = torch.from_numpy(np.ascontiguousarray(bag_idx[lo:hi])).to(device)
+        bag_t = _large_chunk_bags(bag_idx, lo, hi, X, n, seed, bootstrap,
+                                  tree_id_offset)
         fs_t = torch.from_numpy(fs[lo:hi]).to(device)
         (feat, value, right, count, ncount, hidx, hw, off64,
          depth) = ext.build_extended_forest_large(

@@ -189,6 +189,23 @@ void launch_shap_forest(RowDtype dt, bool table_lds, bool acc_lds,
                         int rows_lds, int finalize, size_t lds, int blocks,
                         hipStream_t stream);
 
+// bag_kernels.hip
+int launch_bag_sample_lds(int64_t* out, int32_t* err, uint64_t seed,
+                          uint32_t tree0, int32_t T, uint32_t N, int32_t n,
+                          int64_t row_offset, uint32_t cap, int threads,
+                          hipStream_t stream);
+void launch_bag_global_round(int64_t* out, uint8_t* lose,
+                             unsigned long long* tabs, int32_t* err,
+                             int32_t* total, uint64_t seed, uint32_t tree0,
+                             int32_t T, uint32_t N, int32_t n,
+                             int64_t row_offset, uint32_t cap, int32_t round,
+                             hipStream_t stream);
+void launch_bag_bootstrap(int64_t* out, uint64_t seed, uint32_t tree0,
+                          uint32_t N, int64_t T, int64_t n, int64_t row_offset,
+                          hipStream_t stream);
+void launch_bag_dense_keys(int64_t* keys, uint64_t seed, uint32_t tree0,
+                           int64_t T, int64_t N, hipStream_t stream);
+
 }  // namespace ifa
 
 namespace {
@@ -447,6 +464,121 @@ torch::Tensor bag_gather(torch::Tensor X, torch::Tensor bag_idx) {
                          bag_idx.data_ptr<int64_t>(), bags.data_ptr<float>(),
                          T, n, d, xl.rs, xl.cs, current_stream());
   return bags;
+}
+
+// ---------------------------------------------------------------------------
+// on-device bag sampling (bag_kernels.hip): every route fills a caller-made
+// int64 [T, n] tensor with cpu_engine.sample_bags' rows for the trees
+// tree_id_offset .. tree_id_offset + T - 1
+// ---------------------------------------------------------------------------
+
+namespace {
+
+// largest bag whose hash table (8 bytes * next power of two >= 2n = 128 KB)
+// fits the LDS budget next to the kernel's static words
+constexpr int64_t kBagLdsMaxSamples = 8192;
+constexpr int kBagMaxAttempt = 256;  // cpu_engine.sample_bags' round bound
+const char* const kBagNoConverge =
+    "bag sampling failed to converge (internal bug)";
+
+int64_t bag_table_cap(int64_t n) {
+  int64_t cap = 2;
+  while (cap < 2 * n) cap <<= 1;
+  return cap;
+}
+
+struct BagShape {
+  int64_t T, n;
+};
+
+BagShape check_bag_out(const torch::Tensor& out, int64_t N,
+                       int64_t tree_id_offset, int64_t row_offset) {
+  CHECK_CUDA(out);
+  CHECK_CONTIG(out);
+  TORCH_CHECK(out.dim() == 2 && out.scalar_type() == torch::kInt64,
+              "out must be int64 [T, n]");
+  BagShape s{out.size(0), out.size(1)};
+  TORCH_CHECK(s.T >= 1 && s.n >= 1, "out must hold at least one slot");
+  // draws are 32-bit and the all-ones word marks an empty table entry
+  TORCH_CHECK(N >= 1 && N <= (int64_t)UINT32_MAX,
+              "device bag sampling needs 1 <= total_rows <= 2^32 - 1");
+  TORCH_CHECK(tree_id_offset >= 0 && s.T <= (int64_t)INT_MAX &&
+                  s.T + tree_id_offset <= (int64_t)INT_MAX,
+              "tree ids must fit int32");
+  TORCH_CHECK(row_offset >= 0 && row_offset <= INT64_MAX - N,
+              "row_offset + total_rows overflows int64");
+  return s;
+}
+
+}  // namespace
+
+int64_t bag_sample_lds(torch::Tensor out, int64_t total_rows, int64_t seed,
+                       int64_t tree_id_offset, int64_t row_offset,
+                       int64_t threads) {
+  const BagShape s = check_bag_out(out, total_rows, tree_id_offset, row_offset);
+  TORCH_CHECK(2 * s.n <= total_rows, "the table routes need 2n <= total_rows");
+  TORCH_CHECK(s.n <= kBagLdsMaxSamples, "bag too large for the LDS table");
+  TORCH_CHECK(threads == 0 ||
+                  (threads >= 64 && threads <= 1024 && threads % 64 == 0),
+              "threads must be 0 or a multiple of 64 in [64, 1024]");
+  const int64_t cap = bag_table_cap(s.n);
+  TORCH_CHECK((size_t)cap * 8 + 64 <= kMaxLds, "bag LDS request too large");
+  auto err = torch::zeros({1}, out.options().dtype(torch::kInt32));
+  const int spt = ifa::launch_bag_sample_lds(
+      out.data_ptr<int64_t>(), err.data_ptr<int32_t>(), (uint64_t)seed,
+      (uint32_t)tree_id_offset, (int32_t)s.T, (uint32_t)total_rows,
+      (int32_t)s.n, row_offset, (uint32_t)cap, (int)threads, current_stream());
+  TORCH_CHECK(err.item<int32_t>() == 0, kBagNoConverge);
+  return spt;
+}
+
+// returns the number of redraw rounds it ran (0: the first draws were distinct)
+int64_t bag_sample_global(torch::Tensor out, int64_t total_rows, int64_t seed,
+                          int64_t tree_id_offset, int64_t row_offset) {
+  const BagShape s = check_bag_out(out, total_rows, tree_id_offset, row_offset);
+  TORCH_CHECK(2 * s.n <= total_rows, "the table routes need 2n <= total_rows");
+  TORCH_CHECK(s.n <= ((int64_t)1 << 30), "maxSamples must be <= 2^30");
+  TORCH_CHECK(s.T <= 65535 && s.T * s.n <= (int64_t)INT_MAX,
+              "too many trees in one chunk");
+  const int64_t cap = bag_table_cap(s.n);
+  auto tabs = torch::full({s.T, cap}, -1, out.options());
+  auto lose = torch::empty({s.T, s.n}, out.options().dtype(torch::kUInt8));
+  // word 0: error flags; word 1 + r: losers after round r
+  auto ctr = torch::zeros({kBagMaxAttempt + 2},
+                          out.options().dtype(torch::kInt32));
+  int32_t* ctr_p = ctr.data_ptr<int32_t>();
+  for (int round = 0; round <= kBagMaxAttempt; ++round) {
+    ifa::launch_bag_global_round(
+        out.data_ptr<int64_t>(), lose.data_ptr<uint8_t>(),
+        (unsigned long long*)tabs.data_ptr<int64_t>(), ctr_p,
+        ctr_p + 1 + round, (uint64_t)seed, (uint32_t)tree_id_offset,
+        (int32_t)s.T, (uint32_t)total_rows, (int32_t)s.n, row_offset,
+        (uint32_t)cap, round, current_stream());
+    auto host = ctr.cpu();  // the round's one host sync
+    const int32_t* h = host.data_ptr<int32_t>();
+    TORCH_CHECK(h[0] == 0, kBagNoConverge);
+    if (h[1 + round] == 0) return round;
+  }
+  TORCH_CHECK(false, kBagNoConverge);
+  return -1;
+}
+
+void bag_bootstrap(torch::Tensor out, int64_t total_rows, int64_t seed,
+                   int64_t tree_id_offset, int64_t row_offset) {
+  const BagShape s = check_bag_out(out, total_rows, tree_id_offset, row_offset);
+  TORCH_CHECK(s.n <= (int64_t)UINT32_MAX, "slot ids must fit 32 bits");
+  ifa::launch_bag_bootstrap(out.data_ptr<int64_t>(), (uint64_t)seed,
+                            (uint32_t)tree_id_offset, (uint32_t)total_rows,
+                            s.T, s.n, row_offset, current_stream());
+}
+
+// keys [T, total_rows]: the composite sort keys of the dense regime
+void bag_dense_keys(torch::Tensor keys, int64_t seed, int64_t tree_id_offset) {
+  const BagShape s = check_bag_out(keys, keys.dim() == 2 ? keys.size(1) : 0,
+                                   tree_id_offset, 0);
+  ifa::launch_bag_dense_keys(keys.data_ptr<int64_t>(), (uint64_t)seed,
+                             (uint32_t)tree_id_offset, s.T, s.n,
+                             current_stream());
 }
 
 std::vector<torch::Tensor> build_forest(torch::Tensor bags,
@@ -1394,6 +1526,24 @@ torch::Tensor shap_forest(torch::Tensor X, torch::Tensor table,
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bag_gather", &bag_gather, "gather per-tree bags (K9/K10)");
+  m.def("bag_sample_lds", &bag_sample_lds,
+        "draw bags without replacement, one block per tree, table in LDS; "
+        "returns the slots per thread it ran with (0: state in the row)",
+        py::arg("out"), py::arg("total_rows"), py::arg("seed"),
+        py::arg("tree_id_offset"), py::arg("row_offset"),
+        py::arg("threads") = 0);
+  m.def("bag_sample_global", &bag_sample_global,
+        "draw bags without replacement, table in global memory; returns the "
+        "redraw rounds",
+        py::arg("out"), py::arg("total_rows"), py::arg("seed"),
+        py::arg("tree_id_offset"), py::arg("row_offset"));
+  m.def("bag_bootstrap", &bag_bootstrap, "draw bags with replacement",
+        py::arg("out"), py::arg("total_rows"), py::arg("seed"),
+        py::arg("tree_id_offset"), py::arg("row_offset"));
+  m.def("bag_dense_keys", &bag_dense_keys,
+        "composite sort keys of the dense regime (2n > N)", py::arg("keys"),
+        py::arg("seed"), py::arg("tree_id_offset"));
+  m.attr("BAG_LDS_MAX_SAMPLES") = kBagLdsMaxSamples;
   m.def("build_forest", &build_forest, "build standard iTrees (K1/K2/K11)");
   m.def("build_extended_forest", &build_extended_forest,
         "build extended iTrees (K3-K5)");

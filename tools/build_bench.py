@@ -8,10 +8,12 @@ Usage: python tools/build_bench.py [--rows 2000000] [--features 32]
 
 Fits one estimator on a resident [N, d] CUDA matrix and reports the phase
 fit() times as `bag+build`, split into the host-side draws
-(cpu_engine.sample_bags + feature_subsets) and the rest, which is the tree
-build itself with its uploads and downloads: the HIP builders on a GPU route,
-`X.float().cpu()` plus the CPU oracle where fit() falls back to it. The tool
-only uses the public estimators, so it runs unchanged on older commits.
+(cpu_engine.sample_bags + feature_subsets), the device sampler
+(gpu_engine.sample_bags_device, synchronised; IFA_BAG_DEVICE=0 keeps the bags
+on the host) and the rest, which is the tree build itself with its uploads
+and downloads: the HIP builders on a GPU route, `X.float().cpu()` plus the
+CPU oracle where fit() falls back to it. The tool only uses the public
+estimators, so it runs unchanged on older commits.
 
 --threads-sweep re-times one launch of the large-bag binding alone (the
 first chunk of the same bags, outputs left on the device) at the given block
@@ -81,6 +83,22 @@ def main():
     timed("sample_bags")
     timed("feature_subsets")
 
+    # the device sampler, synchronised so the time is the kernels' and not
+    # the enqueue's (commits that have it)
+    dev_draws = {"s": 0.0, "calls": 0}
+    device_sampler = getattr(gpu_engine, "sample_bags_device", None)
+    if device_sampler is not None:
+        def timed_device(*a, **kw):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = device_sampler(*a, **kw)
+            torch.cuda.synchronize()
+            dev_draws["s"] += time.perf_counter() - t0
+            dev_draws["calls"] += 1
+            return res
+
+        gpu_engine.sample_bags_device = timed_device
+
     cls = ExtendedIsolationForest if args.kind == "extended" else IsolationForest
     kw = {}
     if args.kind == "extended" and args.extension_level is not None:
@@ -108,9 +126,13 @@ def main():
         "fit_s": round(t_fit, 4),
         "bag_build_s": round(phase_s, 4),
         "host_draws_s": round(draws["s"], 4),
-        "build_s": round(phase_s - draws["s"], 4),
-        "build_ms_per_tree": round((phase_s - draws["s"]) * 1e3 / args.trees, 3),
-        "draws_ms_per_tree": round(draws["s"] * 1e3 / args.trees, 3),
+        "device_draws_s": round(dev_draws["s"], 4),
+        "bags": "device" if dev_draws["calls"] else "host",
+        "build_s": round(phase_s - draws["s"] - dev_draws["s"], 4),
+        "build_ms_per_tree": round(
+            (phase_s - draws["s"] - dev_draws["s"]) * 1e3 / args.trees, 3),
+        "draws_ms_per_tree": round(
+            (draws["s"] + dev_draws["s"]) * 1e3 / args.trees, 3),
         "nodes_per_tree": round(float(model.forest.node_count.mean()), 1),
         "height_limit": int(math.ceil(math.log2(max(n, 2)))),
     }
@@ -127,8 +149,11 @@ def main():
         max_nodes = 2 ** (H + 1) - 1 if extended else 2 * n - 1
         per_tree = 16 * n + (28 + (8 * nnz if extended else 0)) * max_nodes
         Tk = gpu_engine._large_chunk_trees(args.trees, per_tree, None)
-        bag_t = torch.from_numpy(
-            np.ascontiguousarray(kept["sample_bags"][:Tk])).to(dev)
+        if "sample_bags" in kept:
+            bag_t = torch.from_numpy(
+                np.ascontiguousarray(kept["sample_bags"][:Tk])).to(dev)
+        else:  # fit() drew on the device: draw the first chunk again
+            bag_t = device_sampler(args.rows, Tk, n, 3, False, device=dev)
         fs_t = torch.from_numpy(np.ascontiguousarray(
             kept["feature_subsets"][:Tk], dtype=np.int32)).to(dev)
         lut = gpu_engine._leaf_lut(n, X.device)
