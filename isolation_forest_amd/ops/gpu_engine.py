@@ -28,6 +28,11 @@ width and dtype (score_extended_forest):
 * otherwise (wide d, ragged widths, LDS overflow) -> the general
   strict-order kernel; forests past the packed 15-bit-node/12-bit-
   feature caps use the wide int4 kernels.
+
+Standard forests past the 15-bit node ids (maxSamples > 16384) score through
+compact level-order records, top levels in LDS and the tail from L2
+(score_forest_deep; large_score_route), and fall back to the wide kernel
+past that format's own caps.
 """
 
 from __future__ import annotations
@@ -35,6 +40,7 @@ from __future__ import annotations
 import logging
 import math
 import os
+import types
 
 import numpy as np
 import torch
@@ -361,7 +367,8 @@ def build_forest_large(X: torch.Tensor, bag_idx,
     ``[T, n, d]`` gather is made, and the trees are built ``chunk_trees`` at
     a time (``None``: as many as ``BUILD_LARGE_BUDGET_BYTES`` holds). The
     forest is bitwise ``cpu_engine.build_forest``'s. It carries no device
-    tensors: forests this size score through the host-packed wide formats.
+    tensors: forests this size score through the deep records (standard;
+    large_score_route) or the host-packed wide formats.
     ``return_depth=True`` returns ``(forest, depth)`` with the kernel's
     per-node depths ``[T, max_nodes]``. ``bag_idx`` is a numpy matrix, an
     int64 tensor on X's device, or ``None``: each chunk's bags are then drawn
@@ -756,6 +763,38 @@ def _nodes_packed_wide(forest, bf16):
     live = internal | leaf
     max_depth = int(depth[live].max()) if live.any() else 0
     return packed, max(max_depth, 1)
+
+
+def _nodes_deep_host(forest, kind):
+    """Host half of the deep pack (ops/hip/deep_kernels.hip): the pre-order
+    arrays TRIMMED to the largest node_count, as three int32 matrices
+    [T, M0] (feature id, -1 for leaves and dead slots; pre-order right
+    child; integer key threshold of the row kind for an internal node, f32
+    bits of depth + c(m) for a leaf), the node counts and the forest's
+    depth. Same key and leaf-value math as _nodes_packed_wide, on 2n - 1
+    minus the padding columns; deep_level_order reorders on the device."""
+    nc = np.ascontiguousarray(forest.node_count, dtype=np.int32)
+    m0 = max(int(nc.max(initial=1)), 1)
+    feat = np.ascontiguousarray(forest.feature[:, :m0])
+    right = np.ascontiguousarray(forest.right[:, :m0], dtype=np.int32)
+    internal = feat >= 0
+    leaf = feat == Forest.LEAF
+    depth = _node_depths(feat, right)
+    w = np.zeros(feat.shape, dtype=np.uint32)
+    if internal.any():
+        v64 = getattr(forest, "value64", None)
+        trimmed = types.SimpleNamespace(
+            value=forest.value[:, :m0],
+            value64=None if v64 is None else v64[:, :m0])
+        w[internal] = _threshold_keys(
+            _split_thresholds32(trimmed)[internal], kind)
+    leafval = depth.astype(np.float32) + forest.value[:, :m0].astype(
+        np.float32)
+    w[leaf] = leafval[leaf].astype(np.float32).view(np.uint32)
+    live = internal | leaf
+    max_depth = int(depth[live].max()) if live.any() else 0
+    return (np.where(internal, feat, -1).astype(np.int32), right,
+            w.view(np.int32), nc, max(max_depth, 1))
 
 
 def _nodes_packed_explain(forest, d_sentinel: int, bf16):
@@ -1298,7 +1337,8 @@ def _device_forest(model, device, v4_key=None):
     """Cached device copy of the packed forest. v4_key = (d, kind) selects
     the standard-scoring v4 packing; None = the EIF packing. Packs that
     hold integer key thresholds — (d, kind), ("wide", kind),
-    ("eif0", d, kind), ("explain", d, kind), ("shap", d, kind) — are keyed
+    ("deep", d, stage, kind), ("eif0", d, kind), ("explain", d, kind),
+    ("shap", d, kind) — are keyed
     on the row KIND, not on "is it 16-bit": bf16 and fp16 keys differ, and
     u32 records under a u16 kernel score silently wrong. The "shap" entry
     is (table words, per-tree word offsets, {host offsets, weights})."""
@@ -1431,6 +1471,19 @@ def _device_forest(model, device, v4_key=None):
                 np.ascontiguousarray(forest.node_count, dtype=np.int32)
             ).to(device)
             extra["height"] = max_depth
+        elif isinstance(v4_key, tuple) and v4_key[0] == "deep":
+            # ("deep", d, stage, kind): aos = the level-order records,
+            # ncount = lds_levels, both made on the device
+            from . import load_extension as _packing_extension
+
+            feat, right, w, nc, max_depth = _nodes_deep_host(
+                forest, v4_key[3])
+            aos, ncount = _packing_extension().deep_level_order(
+                torch.from_numpy(feat).to(device),
+                torch.from_numpy(right).to(device),
+                torch.from_numpy(w).to(device),
+                torch.from_numpy(nc).to(device), v4_key[1], v4_key[2])
+            extra["height"] = max_depth
         elif v4_key == "eif_wide":
             packed = _eif_packed_wide(forest)
             aos = torch.from_numpy(packed).to(device)
@@ -1484,6 +1537,48 @@ def _packed_fits(forest, d: int) -> bool:
     return int(forest.feature.max(initial=0)) <= 4094 and d <= 4094
 
 
+# Largest node_count the deep records hold: links are 20 bits.
+DEEP_MAX_NODES = 1 << 20
+
+
+def _deep_fits(forest, d: int) -> bool:
+    """True when the deep records (ops/hip/deep_kernels.hip) can represent
+    this standard forest: 20-bit links over the TRIMMED trees (node_count,
+    not the 2n - 1 array width), 12-bit feature ids with d as the leaf
+    sentinel."""
+    if isinstance(forest, ExtendedForest):
+        return False
+    if int(np.max(forest.node_count, initial=1)) > DEEP_MAX_NODES:
+        return False
+    fmax = getattr(forest, "_feature_max", None)
+    if fmax is None:  # a pass over [T, 2n - 1]: once per forest
+        fmax = forest._feature_max = int(forest.feature.max(initial=0))
+    return fmax <= 4094 and d <= 4094
+
+
+def _deep_stage(kind: str, d: int) -> int:
+    """Records per tree the deep walk stages for these rows now (0: the key
+    tile leaves no room). Asked of the package's extension, like the packing
+    helpers: a routing proxy installed on this module sees scoring calls."""
+    from . import load_extension as _packing_extension
+
+    return int(_packing_extension().deep_stage(kind, int(d)))
+
+
+def large_score_route(forest, d: int, dtype) -> str:
+    """The kernel family ``score_forest`` runs for a standard forest past the
+    packed 15-bit node ids: ``"deep"`` (compact level-order records, top
+    levels in LDS, tail from L2) or ``"wide"`` (int4 records, one global read
+    per visit). ``IFA_SCORE_DEEP=0`` keeps the wide route; so do forests past
+    ``DEEP_MAX_NODES`` nodes a tree or 4094 features, and rows too wide for
+    the key tile to leave a stage in LDS."""
+    if os.environ.get("IFA_SCORE_DEEP", "1") == "0":
+        return "wide"
+    if not _deep_fits(forest, d):
+        return "wide"
+    return "deep" if _deep_stage(_row_kind(dtype), d) > 0 else "wide"
+
+
 def score_forest(model, X: torch.Tensor, finalize: bool = True) -> torch.Tensor:
     ext = load_extension()
     forest = model.forest
@@ -1491,7 +1586,15 @@ def score_forest(model, X: torch.Tensor, finalize: bool = True) -> torch.Tensor:
     kind = _row_kind(X.dtype)
     c = float(avg_path_length(forest.num_samples))
     if not _packed_fits(forest, d):
-        # loaded/CPU-built forests past the packed-format caps: wide int4
+        if large_score_route(forest, d, kind) == "deep":
+            stage = _deep_stage(kind, d)
+            records, lds_levels, extra = _device_forest(
+                model, X.device, v4_key=("deep", d, stage, kind))
+            return ext.score_forest_deep(
+                _rows_in_place(X), records, lds_levels, forest.num_trees,
+                extra["height"], stage, c, finalize,
+            )
+        # past the deep records' caps too (or IFA_SCORE_DEEP=0): wide int4
         # records, no field-width limits
         aos, ncount, extra = _device_forest(
             model, X.device, v4_key=("wide", kind))

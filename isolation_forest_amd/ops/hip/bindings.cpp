@@ -189,6 +189,22 @@ void launch_shap_forest(RowDtype dt, bool table_lds, bool acc_lds,
                         int rows_lds, int finalize, size_t lds, int blocks,
                         hipStream_t stream);
 
+// deep_kernels.hip
+void launch_deep_level_order(const int32_t* feat, const int32_t* right,
+                             const int32_t* w, const int32_t* ncount,
+                             uint32_t* front_a, uint32_t* front_b, void* out,
+                             int32_t* lds_levels, int32_t T, int32_t Tpad,
+                             int32_t M0, int32_t M, int32_t S, int32_t d,
+                             hipStream_t stream);
+hipError_t launch_score_forest_deep(RowDtype dt, int rpt, const void* X,
+                                    const void* nodes,
+                                    const int32_t* lds_levels, float* out,
+                                    int64_t N, int32_t d, int64_t rs,
+                                    int64_t cs, int32_t Tpad, int32_t M,
+                                    int32_t S, int32_t height, float fT,
+                                    float c_norm, int finalize, size_t lds,
+                                    int blocks, hipStream_t stream);
+
 // bag_kernels.hip
 int launch_bag_sample_lds(int64_t* out, int32_t* err, uint64_t seed,
                           uint32_t tree0, int32_t T, uint32_t N, int32_t n,
@@ -1247,6 +1263,151 @@ torch::Tensor score_forest_wide(torch::Tensor X, torch::Tensor nodes_wide,
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// standard forests past the 15-bit node ids (deep_kernels.hip): compact
+// level-order records, the first `stage` records of every tree walked from
+// LDS and the rest from L2
+// ---------------------------------------------------------------------------
+
+constexpr int kDeepPhase = 4;                // trees per barrier phase
+constexpr int64_t kDeepMaxNodes = 1 << 20;   // links are 20 bits
+constexpr int kDeepStage = 1024;             // records staged per tree
+constexpr int kDeepMinStage = 64;
+
+struct DeepCfg {
+  int rpt, stage;  // stage 0: the key tile leaves no room for a stage
+  size_t lds;
+};
+
+// Rows per thread and the stage S (a power of two) from the LDS left beside
+// the key tile: the largest S up to kDeepStage that keeps two blocks
+// resident per CU, at two rows per thread before one; then the same with one
+// resident block. IFA_DEEP_STAGE=<records> forces S to any power of two >= 2
+// (tests reach the tail walk at small sizes with it); a forced S that does
+// not fit leaves no route.
+DeepCfg pick_deep_cfg(int elem_bytes, int64_t d) {
+  int forced = 0;
+  if (const char* e = getenv("IFA_DEEP_STAGE")) {
+    const long v = atol(e);
+    if (v >= 2 && v <= kDeepMaxNodes && (v & (v - 1)) == 0) forced = (int)v;
+  }
+  const size_t slabs = (size_t)d + 1;
+  for (size_t budget : {kMaxLds / 2, (size_t)150 * 1024}) {
+    for (int s = forced ? forced : kDeepStage;
+         s >= (forced ? forced : kDeepMinStage); s >>= 1) {
+      for (int rpt : {2, 1}) {
+        const size_t l = (size_t)rpt * 256 * slabs * (size_t)elem_bytes +
+                         (size_t)kDeepPhase * s * 8;
+        if (l <= budget) return {rpt, s, l};
+      }
+    }
+  }
+  return {0, 0, 0};
+}
+
+int elem_bytes_of(const std::string& dtype) {
+  TORCH_CHECK(dtype == "bf16" || dtype == "f16" || dtype == "f32",
+              "dtype must be bf16, f16 or f32");
+  return dtype == "f32" ? 4 : 2;
+}
+
+// the stage score_forest_deep runs rows of this kind and width with now, or
+// 0 where it has no route for them
+int64_t deep_stage(const std::string& dtype, int64_t d) {
+  if (d < 1 || d > 4094) return 0;
+  return pick_deep_cfg(elem_bytes_of(dtype), d).stage;
+}
+
+// trimmed pre-order arrays [T, M0] (feature id or < 0 for a leaf, pre-order
+// right child, key threshold or leaf value bits) -> the deep records
+// int32 [Tpad, M, 2] and lds_levels int32 [Tpad] for a stage of `stage`
+std::pair<torch::Tensor, torch::Tensor> deep_level_order(
+    torch::Tensor feat, torch::Tensor right, torch::Tensor w,
+    torch::Tensor ncount, int64_t d, int64_t stage) {
+  for (const torch::Tensor* a : {&feat, &right, &w}) {
+    CHECK_CUDA(*a);
+    CHECK_CONTIG(*a);
+    TORCH_CHECK(a->dim() == 2 && a->scalar_type() == torch::kInt32 &&
+                    a->sizes() == feat.sizes(),
+                "feat, right and w must be int32 [T, M0]");
+  }
+  CHECK_CUDA(ncount);
+  CHECK_CONTIG(ncount);
+  const int64_t T = feat.size(0), M0 = feat.size(1);
+  TORCH_CHECK(ncount.scalar_type() == torch::kInt32 && ncount.dim() == 1 &&
+                  ncount.size(0) == T,
+              "ncount must be int32 [T]");
+  TORCH_CHECK(M0 >= 1 && M0 <= kDeepMaxNodes, "deep links are 20 bits");
+  TORCH_CHECK(d >= 1 && d <= 4094, "deep feature ids are 12 bits, with d "
+                                   "the leaf sentinel");
+  TORCH_CHECK(stage >= 2 && stage <= kDeepMaxNodes &&
+                  (stage & (stage - 1)) == 0,
+              "stage must be a power of two >= 2");
+  TORCH_CHECK(T <= 65535 * kDeepPhase, "too many trees");
+  const int64_t Tpad = (T + kDeepPhase - 1) / kDeepPhase * kDeepPhase;
+  const int64_t M = (M0 + 1) & ~(int64_t)1;
+  auto out = torch::empty({Tpad, M, 2}, feat.options());
+  auto levels = torch::empty({Tpad}, feat.options());
+  if (T == 0) return {out, levels};
+  auto front = torch::empty({2, T, M0}, feat.options());
+  int32_t* fr = front.data_ptr<int32_t>();
+  ifa::launch_deep_level_order(
+      feat.data_ptr<int32_t>(), right.data_ptr<int32_t>(),
+      w.data_ptr<int32_t>(), ncount.data_ptr<int32_t>(), (uint32_t*)fr,
+      (uint32_t*)(fr + T * M0), out.data_ptr<int32_t>(),
+      levels.data_ptr<int32_t>(), (int32_t)T, (int32_t)Tpad, (int32_t)M0,
+      (int32_t)M, (int32_t)stage, (int32_t)d, current_stream());
+  return {out, levels};
+}
+
+// `stage` is the one the records' lds_levels were counted for
+torch::Tensor score_forest_deep(torch::Tensor X, torch::Tensor records,
+                                torch::Tensor lds_levels, int64_t num_trees,
+                                int64_t height, int64_t stage, double c_norm,
+                                bool finalize) {
+  CHECK_CUDA(X);
+  CHECK_CUDA(records);
+  CHECK_CONTIG(records);
+  CHECK_CUDA(lds_levels);
+  CHECK_CONTIG(lds_levels);
+  check_x(X);
+  const XLayout xl = check_x_layout(X);
+  TORCH_CHECK(records.dim() == 3 && records.size(2) == 2 &&
+                  records.scalar_type() == torch::kInt32,
+              "records must be deep int32 [Tpad, M, 2]");
+  const int64_t N = X.size(0), d = X.size(1);
+  const int64_t Tpad = records.size(0), M = records.size(1);
+  TORCH_CHECK(Tpad % kDeepPhase == 0 && num_trees >= 1 && num_trees <= Tpad,
+              "deep tree count must be padded to the phase");
+  TORCH_CHECK(M >= 2 && M % 2 == 0 && M <= kDeepMaxNodes,
+              "deep records hold an even number of nodes, at most 2^20");
+  TORCH_CHECK(lds_levels.scalar_type() == torch::kInt32 &&
+                  lds_levels.dim() == 1 && lds_levels.size(0) == Tpad,
+              "lds_levels must be int32 [Tpad]");
+  TORCH_CHECK(d >= 1 && d <= 4094, "scoring supports d <= 4094 (12-bit "
+                                   "feature field plus the leaf sentinel)");
+  TORCH_CHECK(height >= 1 && height <= 64, "height out of range");
+  const ifa::RowDtype dt = row_dtype(X);
+  const DeepCfg cfg = pick_deep_cfg(ifa::row_elem_bytes(dt), d);
+  TORCH_CHECK(cfg.stage > 0 && cfg.stage == stage,
+              "the records were staged for ", stage, " records a tree, rows "
+              "of this kind and width run ", cfg.stage);
+  auto out = torch::empty({N}, X.options().dtype(torch::kFloat32));
+  if (N == 0) return out;
+  const int64_t rows_per_block = (int64_t)cfg.rpt * 256;
+  const int blocks = (int)std::min<int64_t>(
+      (N + rows_per_block - 1) / rows_per_block, 8192);
+  const hipError_t err = ifa::launch_score_forest_deep(
+      dt, cfg.rpt, X.data_ptr(), records.data_ptr<int32_t>(),
+      lds_levels.data_ptr<int32_t>(), out.data_ptr<float>(), N, (int32_t)d,
+      xl.rs, xl.cs, (int32_t)Tpad, (int32_t)M, (int32_t)cfg.stage,
+      (int32_t)height, (float)num_trees, (float)c_norm, finalize ? 1 : 0,
+      cfg.lds, blocks, current_stream());
+  TORCH_CHECK(err == hipSuccess, "score_forest_deep launch failed (",
+              cfg.lds, " B of LDS): ", hipGetErrorString(err));
+  return out;
+}
+
 torch::Tensor score_extended_wide(torch::Tensor X, torch::Tensor nodes_wide,
                                   torch::Tensor hidx, torch::Tensor hw,
                                   double c_norm, bool finalize) {
@@ -1594,5 +1755,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-feature path-length attribution, extended forests");
   m.def("shap_forest", &shap_forest,
         "exact path-dependent TreeSHAP values, standard forests");
+  m.def("deep_stage", &deep_stage,
+        "records per tree score_forest_deep stages for (dtype, d); 0: none");
+  m.def("deep_level_order", &deep_level_order,
+        "trimmed pre-order arrays -> deep level-order records, lds_levels");
+  m.def("score_forest_deep", &score_forest_deep,
+        "standard forests past 15-bit node ids: LDS top levels, L2 tail");
   m.attr("WAVE") = 64;
 }

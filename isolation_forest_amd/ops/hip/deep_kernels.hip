@@ -1,0 +1,472 @@
+// MI355X (gfx950, CDNA4) standard scoring for forests past the 15-bit node
+// ids of the v4 and heap records (every maxSamples > 16384): compact
+// level-order records, the top of each tree walked from LDS and the rest
+// from L2 (docs/DESIGN.md §3b). BITWISE equal to cpu_engine.path_lengths,
+// like every standard walk: integer-key compares, tree-order f32 sum.
+//
+// Records ("deep" pack), int2 [Tpad][M], M = the largest node_count (even):
+//   x = feat | link << 12   12-bit feature id, 20-bit link
+//   y = key threshold of the row kind (internal) / f32 bits of depth + c(m)
+// in LEVEL order with the two children of a node adjacent: link is the right
+// child's index, the left child is link - 1, one step is
+//   cur = link - (key < thr).
+// A leaf has link = its own index and feat = d, the sentinel slab of the key
+// tile (all-ones keys), so it compares false and rests where it is. Pad trees
+// (Tpad is a multiple of the phase) are single leaves of value +0.0. The
+// first S records of a tree are its top levels; lds_levels[t] counts the
+// leading levels that lie wholly inside them and hold an internal node.
+//
+// deep_level_order_kernel turns trimmed pre-order arrays into these records:
+// one block per tree, level by level. A block-wide prefix sum over "has
+// children" hands every node of a level the slots of its two children in the
+// next one; the old indices of a level (the frontier) ping-pong between two
+// global scratch rows, so a tree of any size is reordered, not only one that
+// fits in LDS.
+//
+// score_forest_deep: a block of 256 threads owns a tile of RPT * 256 rows,
+// keyed into the feature-major LDS tile of the v4 walk. PH trees per barrier
+// phase: the first S records of each are copied into LDS, then every thread
+// walks its RPT * PH chains
+//   phase A  a fixed number of trips that read only LDS (no flags, no votes;
+//            a chain at a leaf self-loops), reads batched as in v4;
+//   phase B  the remaining levels. A chain is finished once it has read a
+//            record whose link is its own index; finished chains load
+//            nothing, live ones read their 8-byte record from global memory
+//            (L2: all blocks walk the trees in the same order), all loads of
+//            a trip before any use. A wave leaves the loop when none of its
+//            lanes has a live chain. The record that finishes a chain is its
+//            leaf, whose y is the value to add.
+//
+// This TU is torch-free and stands alone, like shap_kernels.hip: the key
+// helpers it shares with forest_kernels.hip are duplicated (namespace
+// ifa::deep) so that the other TU, and the native scorer that links only it,
+// do not change.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "row_dtype.h"
+
+namespace ifa {
+namespace deep {
+
+#define DEEP_BT 256
+#define DEEP_WAVE 64
+
+// IEEE fp16 bits as a type of their own; uint16_t means bf16 bits
+enum class f16_t : uint16_t {};
+
+__device__ __forceinline__ uint32_t key16(uint32_t b) {
+  const uint32_t m = b & 0x7FFFu;
+  uint32_t k = (b & 0x8000u) ? (0x7FFFu - m) : (0x8000u + m);
+  if (m == 0) k = 0x8000u;
+  if (m > 0x7F80u) k = 0xFFFFu;
+  return k;
+}
+__device__ __forceinline__ uint32_t key16_f16(uint32_t b) {
+  const uint32_t m = b & 0x7FFFu;
+  uint32_t k = (b & 0x8000u) ? (0x7FFFu - m) : (0x8000u + m);
+  if (m == 0) k = 0x8000u;
+  if (m > 0x7C00u) k = 0xFFFFu;
+  return k;
+}
+__device__ __forceinline__ uint32_t key32(uint32_t b) {
+  const uint32_t m = b & 0x7FFFFFFFu;
+  uint32_t k = (b & 0x80000000u) ? (0x7FFFFFFFu - m) : (0x80000000u + m);
+  if (m == 0) k = 0x80000000u;
+  if (m > 0x7F800000u) k = 0xFFFFFFFFu;
+  return k;
+}
+
+template <typename KT>
+__device__ __forceinline__ KT key_of_bits(KT b);
+template <>
+__device__ __forceinline__ f16_t key_of_bits<f16_t>(f16_t b) {
+  return (f16_t)(uint16_t)key16_f16((uint32_t)(uint16_t)b);
+}
+template <>
+__device__ __forceinline__ uint16_t key_of_bits<uint16_t>(uint16_t b) {
+  return (uint16_t)key16((uint32_t)b);
+}
+template <>
+__device__ __forceinline__ uint32_t key_of_bits<uint32_t>(uint32_t b) {
+  return key32(b);
+}
+
+// 16-bit keys sit in the high half with the low bits saturated: the sentinel
+// widens to 0xFFFFFFFF and compares false against every y, leaf values too
+__device__ __forceinline__ uint32_t widen_key(uint16_t k) {
+  return ((uint32_t)k << 16) | 0xFFFFu;
+}
+__device__ __forceinline__ uint32_t widen_key(f16_t k) {
+  return widen_key((uint16_t)k);
+}
+__device__ __forceinline__ uint32_t widen_key(uint32_t k) { return k; }
+
+template <typename KT>
+__device__ __forceinline__ KT key_sentinel() { return (KT)~(KT)0; }
+template <>
+__device__ __forceinline__ f16_t key_sentinel<f16_t>() {
+  return (f16_t)0xFFFFu;
+}
+
+__device__ __forceinline__ int rec_feat(int x) { return x & 0xFFF; }
+__device__ __forceinline__ int rec_link(int x) {
+  return (int)((uint32_t)x >> 12);
+}
+__device__ __forceinline__ int2 leaf_rec(int d, int i, int y) {
+  return make_int2(d | (i << 12), y);
+}
+
+extern __shared__ __align__(16) unsigned char smem[];
+
+// ---------------------------------------------------------------------------
+// pre-order -> level order, one block per tree
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(DEEP_BT) deep_level_order_kernel(
+    const int32_t* __restrict__ feat,   // [T][M0] feature id, < 0: leaf
+    const int32_t* __restrict__ right,  // [T][M0] pre-order right child
+    const int32_t* __restrict__ w,      // [T][M0] key threshold / leaf value
+    const int32_t* __restrict__ ncnt,   // [T]
+    uint32_t* __restrict__ front_a,     // [T][M0] scratch: a level's old ids
+    uint32_t* __restrict__ front_b,     // [T][M0]
+    int2* __restrict__ out,             // [Tpad][M]
+    int32_t* __restrict__ lds_levels,   // [Tpad]
+    int32_t T, int32_t M0, int32_t M, int32_t S, int32_t d) {
+  __shared__ int wsum[DEEP_BT / DEEP_WAVE];
+  const int t = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & (DEEP_WAVE - 1), wave = tid / DEEP_WAVE;
+  int2* dst = out + (int64_t)t * M;
+  if (t >= T) {  // pad tree: a single leaf of value +0.0
+    for (int i = tid; i < M; i += DEEP_BT) dst[i] = leaf_rec(d, i, 0);
+    if (tid == 0) lds_levels[t] = 0;
+    return;
+  }
+  const int32_t* sf = feat + (int64_t)t * M0;
+  const int32_t* sr = right + (int64_t)t * M0;
+  const int32_t* sw = w + (int64_t)t * M0;
+  uint32_t* cur = front_a + (int64_t)t * M0;
+  uint32_t* nxt = front_b + (int64_t)t * M0;
+  const int n = min(max(ncnt[t], 1), M0);
+  for (int i = n + tid; i < M; i += DEEP_BT) dst[i] = leaf_rec(d, i, 0);
+  if (tid == 0) cur[0] = 0;
+  __syncthreads();
+
+  int begin = 0, end = 1;  // the current level, in new indices
+  int levels = 0;
+  while (begin < end) {
+    int tail = end;  // next free new index (block-uniform)
+    int level_internal = 0;
+    for (int base = begin; base < end; base += DEEP_BT) {
+      const int i = base + tid;
+      int old = 0, f = -1, r = 0, wv = 0;
+      bool internal = false;
+      if (i < end) {
+        old = min((int)cur[i - begin], n - 1);
+        f = sf[old];
+        r = sr[old];
+        wv = sw[old];
+        // children outside the tree (a malformed record) are not followed,
+        // so every index stays below n
+        internal = f >= 0 && r > old + 1 && r < n;
+      }
+      const uint64_t m = __ballot(internal);
+      if (lane == 0) wsum[wave] = __popcll(m);
+      __syncthreads();
+      int before = 0, total = 0;
+#pragma unroll
+      for (int k = 0; k < DEEP_BT / DEEP_WAVE; ++k) {
+        const int c = wsum[k];
+        if (k < wave) before += c;
+        total += c;
+      }
+      __syncthreads();  // wsum is written again by the next chunk
+      int link = i;
+      if (internal) {
+        const int l =
+            tail + 2 * (before + __popcll(m & ((1ull << lane) - 1ull)));
+        if (l + 1 < n) {
+          nxt[l - end] = (uint32_t)(old + 1);
+          nxt[l + 1 - end] = (uint32_t)r;
+          link = l + 1;
+        }
+      }
+      if (i < end)
+        dst[i] = link != i ? make_int2(f | (link << 12), wv)
+                           : leaf_rec(d, i, wv);
+      tail = min(tail + 2 * total, n);
+      level_internal += total;
+    }
+    __syncthreads();  // the next level's frontier is written
+    if (end <= S && level_internal > 0) ++levels;
+    begin = end;
+    end = tail;
+    uint32_t* sw2 = cur;
+    cur = nxt;
+    nxt = sw2;
+  }
+  // nodes no link reaches (never in a built tree): self-loops, so that every
+  // record of the output is defined and in bounds
+  for (int i = end + tid; i < n; i += DEEP_BT) dst[i] = leaf_rec(d, i, 0);
+  if (tid == 0) lds_levels[t] = levels;
+}
+
+// ---------------------------------------------------------------------------
+// scoring
+// ---------------------------------------------------------------------------
+
+// element offset of block row j inside one slab of the key tile (the v4
+// tile: forest_kernels.hip, v4_tile_slot)
+template <typename KT, int RPT>
+__device__ __forceinline__ int tile_slot(int j) {
+  if (sizeof(KT) == 4) return j;
+  constexpr int P = RPT * 128;
+  return (j % P) * 2 + j / P;
+}
+
+// every thread keys its own rows into the tile; barriers are the caller's
+template <typename KT, int RPT>
+__device__ __forceinline__ void stage_tile(KT* rows, const KT* __restrict__ X,
+                                           int64_t block_row0, int rows_here,
+                                           int32_t d, int64_t rs, int64_t cs) {
+  constexpr int FS = RPT * DEEP_BT;
+  constexpr int EPV = 16 / (int)sizeof(KT);
+  const int tid = threadIdx.x;
+  const bool vec = cs == 1 && d % EPV == 0 && rs % EPV == 0 &&
+                   ((uintptr_t)X & 15) == 0;
+#pragma unroll
+  for (int r = 0; r < RPT; ++r) {
+    const int j = tid + r * DEEP_BT;
+    KT* dst = rows + tile_slot<KT, RPT>(j);
+    if (j < rows_here) {
+      const KT* src = X + (block_row0 + j) * rs;
+      if (vec) {
+        for (int c = 0; c < d; c += EPV) {
+          union { uint4 v; KT e[EPV]; } pc;
+          pc.v = *(const uint4*)(src + c);
+#pragma unroll
+          for (int k = 0; k < EPV; ++k)
+            dst[(c + k) * FS] = key_of_bits<KT>(pc.e[k]);
+        }
+      } else {
+        for (int c = 0; c < d; ++c, src += cs)
+          dst[c * FS] = key_of_bits<KT>(*src);
+      }
+    } else {
+      // tail block: rows past N are walked but never stored
+      for (int c = 0; c < d; ++c) dst[c * FS] = key_sentinel<KT>();
+    }
+    dst[d * FS] = key_sentinel<KT>();  // leaf sentinel slab
+  }
+}
+
+template <typename KT, int RPT, int PH>
+__global__ void __launch_bounds__(DEEP_BT) score_forest_deep_kernel(
+    const KT* __restrict__ X,               // raw bf16/fp16/f32 bits
+    const int2* __restrict__ nodes,         // [Tpad][M] deep records
+    const int32_t* __restrict__ lds_levels, // [Tpad]
+    float* __restrict__ out,                // [N] (path sum or score)
+    int64_t N, int32_t d, int32_t Tpad, int32_t M, int32_t S, int32_t height,
+    float fT, float c_norm, int32_t finalize, int64_t rs, int64_t cs) {
+  constexpr int FS = RPT * DEEP_BT;
+  constexpr int rows_per_iter = RPT * DEEP_BT;
+  const int tid = threadIdx.x;
+  const int staged = min(S, M);  // records of a tree that the stage holds
+
+  int2* tlds = (int2*)smem;  // [PH][S]
+  KT* rows = (KT*)(tlds + PH * S);
+
+  for (int64_t block_row0 = (int64_t)blockIdx.x * rows_per_iter;
+       block_row0 < N; block_row0 += (int64_t)gridDim.x * rows_per_iter) {
+    const int rows_here = (int)min((int64_t)rows_per_iter, N - block_row0);
+
+    __syncthreads();  // previous tile's readers done
+    stage_tile<KT, RPT>(rows, X, block_row0, rows_here, d, rs, cs);
+    // the first phase's barriers order these stores before the walk
+
+    const KT* rb[RPT];
+#pragma unroll
+    for (int r = 0; r < RPT; ++r)
+      rb[r] = rows + tile_slot<KT, RPT>(tid + r * DEEP_BT);
+
+    float psum[RPT];
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) psum[r] = 0.f;
+
+    for (int t = 0; t < Tpad; t += PH) {
+      __syncthreads();  // previous phase's LDS readers done
+      // M is even, so a tree starts on 16 bytes: two records per copy
+#pragma unroll
+      for (int s = 0; s < PH; ++s) {
+        const uint4* src = (const uint4*)(nodes + (int64_t)(t + s) * M);
+        uint4* dst = (uint4*)(tlds + s * S);
+        for (int i = tid; i < staged / 2; i += DEEP_BT) dst[i] = src[i];
+      }
+      // trips that stay inside every tree's stage. 0 levels means the root
+      // is a leaf, which rests at record 0 for any number of trips.
+      int la = height;
+#pragma unroll
+      for (int s = 0; s < PH; ++s) {
+        const int l = lds_levels[t + s];
+        if (l > 0) la = min(la, l);
+      }
+      __syncthreads();
+
+      const int2* nbase[PH];
+#pragma unroll
+      for (int s = 0; s < PH; ++s) nbase[s] = nodes + (int64_t)(t + s) * M;
+
+      int cur[RPT][PH];
+#pragma unroll
+      for (int r = 0; r < RPT; ++r)
+#pragma unroll
+        for (int s = 0; s < PH; ++s) cur[r][s] = 0;
+
+      // ---- phase A: one level of all chains, LDS only --------------------
+      auto visit = [&]() __attribute__((always_inline)) {
+        int2 nd[RPT][PH];
+#pragma unroll
+        for (int r = 0; r < RPT; ++r)
+#pragma unroll
+          for (int s = 0; s < PH; ++s) nd[r][s] = tlds[s * S + cur[r][s]];
+        KT kraw[RPT][PH];
+#pragma unroll
+        for (int r = 0; r < RPT; ++r)
+#pragma unroll
+          for (int s = 0; s < PH; ++s)
+            kraw[r][s] = rb[r][rec_feat(nd[r][s].x) * FS];
+#pragma unroll
+        for (int r = 0; r < RPT; ++r)
+#pragma unroll
+          for (int s = 0; s < PH; ++s)
+            cur[r][s] = rec_link(nd[r][s].x) -
+                        (widen_key(kraw[r][s]) < (uint32_t)nd[r][s].y);
+      };
+      int it = 0;
+      for (; it + 2 <= la; it += 2) {
+        visit();
+        visit();
+      }
+      if (it < la) visit();
+
+      // ---- phase B: the tail ---------------------------------------------
+      // bit r * PH + s of `live`: the chain has not read its leaf yet
+      uint32_t live = (1u << (RPT * PH)) - 1u;
+      int val[RPT][PH];
+      // `first`: the level after the staged ones straddles the stage's end,
+      // and a chain that rested at a leaf in phase A sits inside it: records
+      // below S come from LDS on this trip
+      auto tail_trip = [&](auto first) __attribute__((always_inline)) {
+        int2 nd[RPT][PH];
+#pragma unroll
+        for (int r = 0; r < RPT; ++r)
+#pragma unroll
+          for (int s = 0; s < PH; ++s)
+            if (live & (1u << (r * PH + s))) {
+              if (decltype(first)::value && cur[r][s] < S)
+                nd[r][s] = tlds[s * S + cur[r][s]];
+              else
+                nd[r][s] = nbase[s][cur[r][s]];
+            }
+        KT kraw[RPT][PH];
+#pragma unroll
+        for (int r = 0; r < RPT; ++r)
+#pragma unroll
+          for (int s = 0; s < PH; ++s)
+            if (live & (1u << (r * PH + s)))
+              kraw[r][s] = rb[r][rec_feat(nd[r][s].x) * FS];
+#pragma unroll
+        for (int r = 0; r < RPT; ++r)
+#pragma unroll
+          for (int s = 0; s < PH; ++s)
+            if (live & (1u << (r * PH + s))) {
+              const int link = rec_link(nd[r][s].x);
+              val[r][s] = nd[r][s].y;
+              if (link == cur[r][s])
+                live &= ~(1u << (r * PH + s));
+              else
+                cur[r][s] = link - (widen_key(kraw[r][s]) <
+                                    (uint32_t)nd[r][s].y);
+            }
+      };
+      tail_trip(std::true_type{});
+      // a chain at depth `height` is a leaf: height - la more trips read it
+      for (int k = la; k < height && __any(live != 0); ++k)
+        tail_trip(std::false_type{});
+
+#pragma unroll
+      for (int r = 0; r < RPT; ++r)
+#pragma unroll
+        for (int s = 0; s < PH; ++s)
+          psum[r] = __fadd_rn(psum[r], __int_as_float(val[r][s]));
+    }
+
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+      const int64_t my_row = block_row0 + tid + r * DEEP_BT;
+      if (my_row < N) {
+        if (finalize) {
+          const float mean32 = (float)((double)psum[r] / (double)fT);
+          const double ratio = (double)mean32 / (double)c_norm;
+          out[my_row] = (float)exp2(-ratio);
+        } else {
+          out[my_row] = psum[r];
+        }
+      }
+    }
+  }
+}
+
+}  // namespace deep
+
+// host-side launchers (bindings.cpp is compiled by g++)
+
+void launch_deep_level_order(const int32_t* feat, const int32_t* right,
+                             const int32_t* w, const int32_t* ncount,
+                             uint32_t* front_a, uint32_t* front_b, void* out,
+                             int32_t* lds_levels, int32_t T, int32_t Tpad,
+                             int32_t M0, int32_t M, int32_t S, int32_t d,
+                             hipStream_t stream) {
+  hipLaunchKernelGGL(deep::deep_level_order_kernel, dim3(Tpad), dim3(DEEP_BT),
+                     0, stream, feat, right, w, ncount, front_a, front_b,
+                     (int2*)out, lds_levels, T, M0, M, S, d);
+}
+
+hipError_t launch_score_forest_deep(RowDtype dt, int rpt, const void* X,
+                                    const void* nodes,
+                                    const int32_t* lds_levels, float* out,
+                                    int64_t N, int32_t d, int64_t rs,
+                                    int64_t cs, int32_t Tpad, int32_t M,
+                                    int32_t S, int32_t height, float fT,
+                                    float c_norm, int finalize, size_t lds,
+                                    int blocks, hipStream_t stream) {
+  hipError_t err = hipSuccess;
+#define LDP1(KT, RPT)                                                         \
+  do {                                                                        \
+    const void* fn = (const void*)deep::score_forest_deep_kernel<KT, RPT, 4>; \
+    if (lds > 64 * 1024)                                                      \
+      err = hipFuncSetAttribute(                                              \
+          fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
+    if (err != hipSuccess) return err;                                        \
+    hipLaunchKernelGGL((deep::score_forest_deep_kernel<KT, RPT, 4>),          \
+                       dim3(blocks), dim3(DEEP_BT), lds, stream,              \
+                       (const KT*)X, (const int2*)nodes, lds_levels, out, N,  \
+                       d, Tpad, M, S, height, fT, c_norm, finalize, rs, cs);  \
+  } while (0)
+#define LDP(KT)                                                               \
+  do {                                                                        \
+    if (rpt == 2) LDP1(KT, 2);                                                \
+    else LDP1(KT, 1);                                                         \
+  } while (0)
+  if (dt == ROW_BF16) LDP(uint16_t);
+  else if (dt == ROW_F16) LDP(deep::f16_t);
+  else LDP(uint32_t);
+#undef LDP
+#undef LDP1
+  return hipGetLastError();
+}
+
+}  // namespace ifa
