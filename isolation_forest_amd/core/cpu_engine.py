@@ -775,6 +775,31 @@ def explain_tables(forest):
     return tabs
 
 
+def explain_tables_trimmed(forest):
+    """explain_tables of a standard forest over its first
+    M = max(node_count) columns only: ``bias`` and float32 ``dl``/``dr``
+    [T, M], bit for bit explain_tables' first M columns (pre-order keeps
+    every child of a live node below node_count, so the sweep never looks
+    past them). For forests whose arrays are far wider than their trees
+    (2n - 1 columns, a few thousand nodes): no [T, 2n - 1] float64
+    temporaries. Not cached; the device pack that uses it is."""
+    import types
+
+    m = max(int(np.max(forest.node_count, initial=1)), 1)
+    trimmed = types.SimpleNamespace(
+        feature=forest.feature[:, :m], right=forest.right[:, :m],
+        value=forest.value[:, :m],
+        num_instances=forest.num_instances[:, :m],
+        num_trees=forest.num_trees)
+    E, _ = node_expectations(trimmed)
+    dl64, dr64 = edge_deltas(trimmed, E)
+    bias = (np.float32(E[:, 0].mean()) if forest.num_trees
+            else np.float32(0.0))
+    return {"bias": bias,
+            "dl": np.ascontiguousarray(dl64.astype(np.float32)),
+            "dr": np.ascontiguousarray(dr64.astype(np.float32))}
+
+
 def expected_path_length(forest) -> np.float32:
     """The attribution bias: f32(mean over trees of E[root])."""
     return explain_tables(forest)["bias"]

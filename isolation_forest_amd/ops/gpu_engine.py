@@ -797,6 +797,23 @@ def _nodes_deep_host(forest, kind):
             w.view(np.int32), nc, max(max_depth, 1))
 
 
+def _nodes_explain_deep_host(forest, kind):
+    """Host half of the explain deep pack (ops/hip/deep_kernels.hip):
+    _nodes_deep_host's trimmed pre-order arrays (feature id, right child,
+    key threshold of the row kind) plus the f32 bits of the two edge deltas,
+    int32 [T, M0] each, from cpu_engine.explain_tables_trimmed — the CPU
+    oracle's deltas without its [T, 2n - 1] float64 sweep. Leaf slots of
+    the threshold array still hold _nodes_deep_host's leaf values; the
+    reorder on the device writes threshold 0 into every leaf record.
+    Returns (feat, right, w, dl, dr, node_count, max_depth)."""
+    from ..core.cpu_engine import explain_tables_trimmed
+
+    feat, right, w, nc, max_depth = _nodes_deep_host(forest, kind)
+    tabs = explain_tables_trimmed(forest)
+    return (feat, right, w, np.ascontiguousarray(tabs["dl"]).view(np.int32),
+            np.ascontiguousarray(tabs["dr"]).view(np.int32), nc, max_depth)
+
+
 def _nodes_packed_explain(forest, d_sentinel: int, bf16):
     """16-byte node records for explain_forest_kernel (`bf16` is the row
     kind, as in _nodes_packed_v4):
@@ -1338,7 +1355,7 @@ def _device_forest(model, device, v4_key=None):
     the standard-scoring v4 packing; None = the EIF packing. Packs that
     hold integer key thresholds — (d, kind), ("wide", kind),
     ("deep", d, stage, kind), ("eif0", d, kind), ("explain", d, kind),
-    ("shap", d, kind) — are keyed
+    ("explain_deep", d, stage, kind), ("shap", d, kind) — are keyed
     on the row KIND, not on "is it 16-bit": bf16 and fp16 keys differ, and
     u32 records under a u16 kernel score silently wrong. The "shap" entry
     is (table words, per-tree word offsets, {host offsets, weights})."""
@@ -1484,6 +1501,17 @@ def _device_forest(model, device, v4_key=None):
                 torch.from_numpy(w).to(device),
                 torch.from_numpy(nc).to(device), v4_key[1], v4_key[2])
             extra["height"] = max_depth
+        elif isinstance(v4_key, tuple) and v4_key[0] == "explain_deep":
+            # ("explain_deep", d, stage, kind): as "deep", 16-byte records
+            from . import load_extension as _packing_extension
+
+            feat, right, w, dl, dr, nc, max_depth = _nodes_explain_deep_host(
+                forest, v4_key[3])
+            aos, ncount = _packing_extension().explain_deep_level_order(
+                *(torch.from_numpy(a).to(device)
+                  for a in (feat, right, w, dl, dr, nc)),
+                v4_key[1], v4_key[2])
+            extra["height"] = max_depth
         elif v4_key == "eif_wide":
             packed = _eif_packed_wide(forest)
             aos = torch.from_numpy(packed).to(device)
@@ -1541,6 +1569,15 @@ def _packed_fits(forest, d: int) -> bool:
 DEEP_MAX_NODES = 1 << 20
 
 
+def _feature_max(forest) -> int:
+    """Largest split feature id (0 for a forest of leaves), cached on the
+    forest: a pass over [T, 2n - 1], made once."""
+    fmax = getattr(forest, "_feature_max", None)
+    if fmax is None:
+        fmax = forest._feature_max = int(forest.feature.max(initial=0))
+    return fmax
+
+
 def _deep_fits(forest, d: int) -> bool:
     """True when the deep records (ops/hip/deep_kernels.hip) can represent
     this standard forest: 20-bit links over the TRIMMED trees (node_count,
@@ -1550,10 +1587,7 @@ def _deep_fits(forest, d: int) -> bool:
         return False
     if int(np.max(forest.node_count, initial=1)) > DEEP_MAX_NODES:
         return False
-    fmax = getattr(forest, "_feature_max", None)
-    if fmax is None:  # a pass over [T, 2n - 1]: once per forest
-        fmax = forest._feature_max = int(forest.feature.max(initial=0))
-    return fmax <= 4094 and d <= 4094
+    return _feature_max(forest) <= 4094 and d <= 4094
 
 
 def _deep_stage(kind: str, d: int) -> int:
@@ -1725,9 +1759,32 @@ def score_extended_forest(model, X: torch.Tensor, finalize: bool = True) -> torc
 # ---------------------------------------------------------------------------
 
 
+def _explain_deep_stage(kind: str, d: int) -> int:
+    """Records per tree the deep explain walk stages for these rows now (0:
+    the key tile leaves no room); see _deep_stage."""
+    from . import load_extension as _packing_extension
+
+    return int(_packing_extension().explain_deep_stage(kind, int(d)))
+
+
+def large_explain_route(forest, d: int, dtype) -> str:
+    """Where ``explain_forest`` attributes a forest past the packed 15-bit
+    node ids: ``"deep"`` (explain_forest_deep: 16-byte level-order records,
+    top levels in LDS, tail from L2) or ``"cpu"`` (the oracle, with a logged
+    warning). ``IFA_EXPLAIN_DEEP=0`` keeps the CPU path; so do extended
+    forests, forests past ``DEEP_MAX_NODES`` nodes a tree or 4094 features,
+    and rows too wide for the key tile to leave a stage in LDS."""
+    if os.environ.get("IFA_EXPLAIN_DEEP", "1") == "0":
+        return "cpu"
+    if not _deep_fits(forest, d):
+        return "cpu"
+    return "deep" if _explain_deep_stage(_row_kind(dtype), d) > 0 else "cpu"
+
+
 def _explain_on_cpu(fn, forest, X: torch.Tensor, finalize: bool, why: str):
-    """Forests past the packed-record caps: CPU oracle, result moved to X's
-    device (a correctness path; there are no wide-record explain kernels)."""
+    """Forests past the packed-record caps that the deep explain route does
+    not take either: CPU oracle, result moved to X's device (a correctness
+    path)."""
     _log.warning(
         "feature_contributions: %s; computing on the CPU oracle", why)
     Xc = X.detach().float().cpu().contiguous().numpy()
@@ -1748,11 +1805,21 @@ def explain_forest(model, X: torch.Tensor, finalize: bool = True) -> torch.Tenso
     forest = model.forest
     d = int(X.shape[1])
     _check_explain_input(X)
-    fmax = int(forest.feature.max(initial=-1))
+    # wide arrays (2n - 1 columns past the 15-bit ids): the cached maximum
+    fmax = (_feature_max(forest) if forest.feature.shape[1] > 32767
+            else int(forest.feature.max(initial=-1)))
     if fmax >= d:
         raise ValueError(
             f"the forest splits on feature {fmax} but rows have {d} columns")
     if not _packed_fits(forest, d):
+        kind = _row_kind(X.dtype)
+        if large_explain_route(forest, d, kind) == "deep":
+            stage = _explain_deep_stage(kind, d)
+            records, lds_levels, extra = _device_forest(
+                model, X.device, v4_key=("explain_deep", d, stage, kind))
+            return load_extension().explain_forest_deep(
+                _rows_in_place(X), records, lds_levels, forest.num_trees,
+                extra["height"], stage, finalize)
         return _explain_on_cpu(
             cpu_engine.feature_contributions, forest, X, finalize,
             "forest exceeds the packed node format (15-bit node ids, "

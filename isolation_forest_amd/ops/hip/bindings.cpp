@@ -204,6 +204,20 @@ hipError_t launch_score_forest_deep(RowDtype dt, int rpt, const void* X,
                                     int32_t S, int32_t height, float fT,
                                     float c_norm, int finalize, size_t lds,
                                     int blocks, hipStream_t stream);
+void launch_explain_deep_level_order(
+    const int32_t* feat, const int32_t* right, const int32_t* w,
+    const int32_t* dl, const int32_t* dr, const int32_t* ncount,
+    uint32_t* front_a, uint32_t* front_b, void* out, int32_t* lds_levels,
+    int32_t T, int32_t Tpad, int32_t M0, int32_t M, int32_t S, int32_t d,
+    hipStream_t stream);
+hipError_t launch_explain_forest_deep(RowDtype dt, int rpt, bool acc_lds,
+                                      const void* X, const void* nodes,
+                                      const int32_t* lds_levels, float* out,
+                                      int64_t N, int32_t d, int64_t rs,
+                                      int64_t cs, int32_t Tpad, int32_t M,
+                                      int32_t S, int32_t height, float fT,
+                                      int finalize, size_t lds, int blocks,
+                                      hipStream_t stream);
 
 // bag_kernels.hip
 int launch_bag_sample_lds(int64_t* out, int32_t* err, uint64_t seed,
@@ -1408,6 +1422,170 @@ torch::Tensor score_forest_deep(torch::Tensor X, torch::Tensor records,
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// attribution for the same forests (explain_forest_deep_kernel): 16-byte
+// level-order records that carry the two edge deltas
+// ---------------------------------------------------------------------------
+
+constexpr int kXDeepStage = 512;          // records staged per tree: 8 KB
+constexpr int kXDeepGlobalStage = 1024;   // beside accumulators in out
+constexpr int kXDeepMinStage = 64;
+
+struct ExplainDeepCfg {
+  int rpt, stage;  // stage 0: the key tile leaves no room for a stage
+  bool acc_lds;
+  size_t lds;
+};
+
+// The stage S and the accumulator route, from the LDS left beside the key
+// tile (profiles/explain_deep.md has the timings behind the order):
+//  1. two rows a thread with the f32 accumulator tile [d + 1][512] in LDS:
+//     the largest S up to kXDeepStage that keeps two blocks resident per CU,
+//     then the same with one resident block;
+//  2. the tile does not fit, or IFA_EXPLAIN_FORCE_GLOBAL_ACC=1: the adds go
+//     to out[N, d] itself, at one row a thread and the largest S up to
+//     kXDeepGlobalStage that one block holds: the cells a CU adds into stay
+//     L2-resident only while few rows are in flight.
+// IFA_EXPLAIN_DEEP_STAGE=<records> forces S to any power of two >= 2; a
+// forced S that fits neither route leaves none.
+ExplainDeepCfg pick_explain_deep_cfg(int elem_bytes, int64_t d) {
+  int forced = 0;
+  if (const char* e = getenv("IFA_EXPLAIN_DEEP_STAGE")) {
+    const long v = atol(e);
+    if (v >= 2 && v <= kDeepMaxNodes && (v & (v - 1)) == 0) forced = (int)v;
+  }
+  bool force_global = false;
+  if (const char* e = getenv("IFA_EXPLAIN_FORCE_GLOBAL_ACC"))
+    force_global = atoi(e) != 0;
+  const size_t slabs = (size_t)d + 1;
+  const size_t one_block = (size_t)150 * 1024;
+  if (!force_global) {
+    const size_t tiles = (size_t)2 * 256 * slabs * ((size_t)elem_bytes + 4);
+    for (size_t budget : {kMaxLds / 2, one_block})
+      for (int s = forced ? forced : kXDeepStage;
+           s >= (forced ? forced : kXDeepMinStage); s >>= 1) {
+        const size_t l = tiles + (size_t)kDeepPhase * s * 16;
+        if (l <= budget) return {2, s, true, l};
+      }
+  }
+  for (int s = forced ? forced : kXDeepGlobalStage;
+       s >= (forced ? forced : kXDeepMinStage); s >>= 1) {
+    const size_t l = (size_t)256 * slabs * (size_t)elem_bytes +
+                     (size_t)kDeepPhase * s * 16;
+    if (l <= one_block) return {1, s, false, l};
+  }
+  return {0, 0, false, 0};
+}
+
+// the stage explain_forest_deep runs rows of this kind and width with now,
+// or 0 where it has no route for them
+int64_t explain_deep_stage(const std::string& dtype, int64_t d) {
+  if (d < 1 || d > 4094) return 0;
+  return pick_explain_deep_cfg(elem_bytes_of(dtype), d).stage;
+}
+
+// trimmed pre-order arrays [T, M0] (deep_level_order's three, plus the f32
+// bits of the two edge deltas) -> the explain deep records int32 [Tpad, M, 4]
+// and lds_levels int32 [Tpad] for a stage of `stage`. M = M0: a 16-byte
+// record is one piece of the stage copy.
+std::pair<torch::Tensor, torch::Tensor> explain_deep_level_order(
+    torch::Tensor feat, torch::Tensor right, torch::Tensor w, torch::Tensor dl,
+    torch::Tensor dr, torch::Tensor ncount, int64_t d, int64_t stage) {
+  for (const torch::Tensor* a : {&feat, &right, &w, &dl, &dr}) {
+    CHECK_CUDA(*a);
+    CHECK_CONTIG(*a);
+    TORCH_CHECK(a->dim() == 2 && a->scalar_type() == torch::kInt32 &&
+                    a->sizes() == feat.sizes(),
+                "feat, right, w, dl and dr must be int32 [T, M0]");
+  }
+  CHECK_CUDA(ncount);
+  CHECK_CONTIG(ncount);
+  const int64_t T = feat.size(0), M0 = feat.size(1);
+  TORCH_CHECK(ncount.scalar_type() == torch::kInt32 && ncount.dim() == 1 &&
+                  ncount.size(0) == T,
+              "ncount must be int32 [T]");
+  TORCH_CHECK(M0 >= 1 && M0 <= kDeepMaxNodes, "deep links are 20 bits");
+  TORCH_CHECK(d >= 1 && d <= 4094, "deep feature ids are 12 bits, with d "
+                                   "the leaf sentinel");
+  TORCH_CHECK(stage >= 2 && stage <= kDeepMaxNodes &&
+                  (stage & (stage - 1)) == 0,
+              "stage must be a power of two >= 2");
+  TORCH_CHECK(T <= 65535 * kDeepPhase, "too many trees");
+  const int64_t Tpad = (T + kDeepPhase - 1) / kDeepPhase * kDeepPhase;
+  const int64_t M = M0;
+  auto out = torch::empty({Tpad, M, 4}, feat.options());
+  auto levels = torch::empty({Tpad}, feat.options());
+  if (T == 0) return {out, levels};
+  auto front = torch::empty({2, T, M0}, feat.options());
+  int32_t* fr = front.data_ptr<int32_t>();
+  ifa::launch_explain_deep_level_order(
+      feat.data_ptr<int32_t>(), right.data_ptr<int32_t>(),
+      w.data_ptr<int32_t>(), dl.data_ptr<int32_t>(), dr.data_ptr<int32_t>(),
+      ncount.data_ptr<int32_t>(), (uint32_t*)fr, (uint32_t*)(fr + T * M0),
+      out.data_ptr<int32_t>(), levels.data_ptr<int32_t>(), (int32_t)T,
+      (int32_t)Tpad, (int32_t)M0, (int32_t)M, (int32_t)stage, (int32_t)d,
+      current_stream());
+  return {out, levels};
+}
+
+// Returns the f32 [N, d] contribution matrix (raw sums when !finalize).
+// `stage` is the one the records' lds_levels were counted for.
+torch::Tensor explain_forest_deep(torch::Tensor X, torch::Tensor records,
+                                  torch::Tensor lds_levels, int64_t num_trees,
+                                  int64_t height, int64_t stage,
+                                  bool finalize) {
+  CHECK_CUDA(X);
+  CHECK_CUDA(records);
+  CHECK_CONTIG(records);
+  CHECK_CUDA(lds_levels);
+  CHECK_CONTIG(lds_levels);
+  check_x(X);
+  const XLayout xl = check_x_layout(X);
+  TORCH_CHECK(records.dim() == 3 && records.size(2) == 4 &&
+                  records.scalar_type() == torch::kInt32,
+              "records must be explain deep int32 [Tpad, M, 4]");
+  const int64_t N = X.size(0), d = X.size(1);
+  const int64_t Tpad = records.size(0), M = records.size(1);
+  TORCH_CHECK(Tpad % kDeepPhase == 0 && num_trees >= 1 && num_trees <= Tpad,
+              "deep tree count must be padded to the phase");
+  TORCH_CHECK(M >= 1 && M <= kDeepMaxNodes,
+              "deep records hold at most 2^20 nodes a tree");
+  TORCH_CHECK(lds_levels.scalar_type() == torch::kInt32 &&
+                  lds_levels.dim() == 1 && lds_levels.size(0) == Tpad,
+              "lds_levels must be int32 [Tpad]");
+  TORCH_CHECK(d >= 1 && d <= 4094,
+              "explain supports 1 <= d <= 4094 (12-bit feature field plus "
+              "the leaf sentinel slab)");
+  TORCH_CHECK(height >= 1 && height <= 64, "height out of range");
+  const ifa::RowDtype dt = row_dtype(X);
+  const ExplainDeepCfg cfg = pick_explain_deep_cfg(ifa::row_elem_bytes(dt), d);
+  TORCH_CHECK(cfg.stage > 0 && cfg.stage == stage,
+              "the records were staged for ", stage, " records a tree, rows "
+              "of this kind and width run ", cfg.stage);
+  const auto out_opts = X.options().dtype(torch::kFloat32);
+  // the LDS-tile flush writes every cell; the global route adds into out
+  auto out = cfg.acc_lds ? torch::empty({N, d}, out_opts)
+                         : torch::zeros({N, d}, out_opts);
+  if (N == 0) return out;
+  int64_t max_blocks = 8192;
+  if (const char* e = getenv("IFA_EXPLAIN_MAX_BLOCKS")) {
+    const int64_t v = atoll(e);
+    if (v >= 1) max_blocks = std::min<int64_t>(v, 8192);
+  }
+  const int64_t rows_per_block = (int64_t)cfg.rpt * 256;
+  const int blocks = (int)std::min<int64_t>(
+      (N + rows_per_block - 1) / rows_per_block, max_blocks);
+  const hipError_t err = ifa::launch_explain_forest_deep(
+      dt, cfg.rpt, cfg.acc_lds, X.data_ptr(), records.data_ptr<int32_t>(),
+      lds_levels.data_ptr<int32_t>(), out.data_ptr<float>(), N, (int32_t)d,
+      xl.rs, xl.cs, (int32_t)Tpad, (int32_t)M, (int32_t)cfg.stage,
+      (int32_t)height, (float)num_trees, finalize ? 1 : 0, cfg.lds, blocks,
+      current_stream());
+  TORCH_CHECK(err == hipSuccess, "explain_forest_deep launch failed (",
+              cfg.lds, " B of LDS): ", hipGetErrorString(err));
+  return out;
+}
+
 torch::Tensor score_extended_wide(torch::Tensor X, torch::Tensor nodes_wide,
                                   torch::Tensor hidx, torch::Tensor hw,
                                   double c_norm, bool finalize) {
@@ -1761,5 +1939,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "trimmed pre-order arrays -> deep level-order records, lds_levels");
   m.def("score_forest_deep", &score_forest_deep,
         "standard forests past 15-bit node ids: LDS top levels, L2 tail");
+  m.def("explain_deep_stage", &explain_deep_stage,
+        "records per tree explain_forest_deep stages for (dtype, d); 0: none");
+  m.def("explain_deep_level_order", &explain_deep_level_order,
+        "trimmed pre-order arrays and edge deltas -> explain deep records, "
+        "lds_levels");
+  m.def("explain_forest_deep", &explain_forest_deep,
+        "attribution past 15-bit node ids: LDS top levels, L2 tail");
   m.attr("WAVE") = 64;
 }

@@ -120,28 +120,50 @@ __device__ __forceinline__ int2 leaf_rec(int d, int i, int y) {
   return make_int2(d | (i << 12), y);
 }
 
+// The level-order kernel writes either record type. The int4 ("explain
+// deep") record carries two more payload words, the f32 bits of the edge
+// deltas; its leaves hold threshold 0 and +0.0 twice whatever w says.
+__device__ __forceinline__ void put_node(int2* dst, int i, int x, int y, int,
+                                         int) {
+  dst[i] = make_int2(x, y);
+}
+__device__ __forceinline__ void put_node(int4* dst, int i, int x, int y, int z,
+                                         int w) {
+  dst[i] = make_int4(x, y, z, w);
+}
+__device__ __forceinline__ void put_leaf(int2* dst, int d, int i, int y) {
+  dst[i] = leaf_rec(d, i, y);
+}
+__device__ __forceinline__ void put_leaf(int4* dst, int d, int i, int) {
+  dst[i] = make_int4(d | (i << 12), 0, 0, 0);
+}
+
 extern __shared__ __align__(16) unsigned char smem[];
 
 // ---------------------------------------------------------------------------
 // pre-order -> level order, one block per tree
 // ---------------------------------------------------------------------------
+template <typename REC>
 __global__ void __launch_bounds__(DEEP_BT) deep_level_order_kernel(
     const int32_t* __restrict__ feat,   // [T][M0] feature id, < 0: leaf
     const int32_t* __restrict__ right,  // [T][M0] pre-order right child
     const int32_t* __restrict__ w,      // [T][M0] key threshold / leaf value
+    const int32_t* __restrict__ pz,     // [T][M0] int4 records: delta_left
+    const int32_t* __restrict__ pw,     // [T][M0] and delta_right bits
     const int32_t* __restrict__ ncnt,   // [T]
     uint32_t* __restrict__ front_a,     // [T][M0] scratch: a level's old ids
     uint32_t* __restrict__ front_b,     // [T][M0]
-    int2* __restrict__ out,             // [Tpad][M]
+    REC* __restrict__ out,              // [Tpad][M]
     int32_t* __restrict__ lds_levels,   // [Tpad]
     int32_t T, int32_t M0, int32_t M, int32_t S, int32_t d) {
   __shared__ int wsum[DEEP_BT / DEEP_WAVE];
   const int t = blockIdx.x;
   const int tid = threadIdx.x;
   const int lane = tid & (DEEP_WAVE - 1), wave = tid / DEEP_WAVE;
-  int2* dst = out + (int64_t)t * M;
+  constexpr bool kPayload = sizeof(REC) == 16;
+  REC* dst = out + (int64_t)t * M;
   if (t >= T) {  // pad tree: a single leaf of value +0.0
-    for (int i = tid; i < M; i += DEEP_BT) dst[i] = leaf_rec(d, i, 0);
+    for (int i = tid; i < M; i += DEEP_BT) put_leaf(dst, d, i, 0);
     if (tid == 0) lds_levels[t] = 0;
     return;
   }
@@ -151,7 +173,7 @@ __global__ void __launch_bounds__(DEEP_BT) deep_level_order_kernel(
   uint32_t* cur = front_a + (int64_t)t * M0;
   uint32_t* nxt = front_b + (int64_t)t * M0;
   const int n = min(max(ncnt[t], 1), M0);
-  for (int i = n + tid; i < M; i += DEEP_BT) dst[i] = leaf_rec(d, i, 0);
+  for (int i = n + tid; i < M; i += DEEP_BT) put_leaf(dst, d, i, 0);
   if (tid == 0) cur[0] = 0;
   __syncthreads();
 
@@ -162,13 +184,17 @@ __global__ void __launch_bounds__(DEEP_BT) deep_level_order_kernel(
     int level_internal = 0;
     for (int base = begin; base < end; base += DEEP_BT) {
       const int i = base + tid;
-      int old = 0, f = -1, r = 0, wv = 0;
+      int old = 0, f = -1, r = 0, wv = 0, zv = 0, yv = 0;
       bool internal = false;
       if (i < end) {
         old = min((int)cur[i - begin], n - 1);
         f = sf[old];
         r = sr[old];
         wv = sw[old];
+        if (kPayload) {
+          zv = pz[(int64_t)t * M0 + old];
+          yv = pw[(int64_t)t * M0 + old];
+        }
         // children outside the tree (a malformed record) are not followed,
         // so every index stays below n
         internal = f >= 0 && r > old + 1 && r < n;
@@ -194,9 +220,12 @@ __global__ void __launch_bounds__(DEEP_BT) deep_level_order_kernel(
           link = l + 1;
         }
       }
-      if (i < end)
-        dst[i] = link != i ? make_int2(f | (link << 12), wv)
-                           : leaf_rec(d, i, wv);
+      if (i < end) {
+        if (link != i)
+          put_node(dst, i, f | (link << 12), wv, zv, yv);
+        else
+          put_leaf(dst, d, i, wv);
+      }
       tail = min(tail + 2 * total, n);
       level_internal += total;
     }
@@ -210,7 +239,7 @@ __global__ void __launch_bounds__(DEEP_BT) deep_level_order_kernel(
   }
   // nodes no link reaches (never in a built tree): self-loops, so that every
   // record of the output is defined and in bounds
-  for (int i = end + tid; i < n; i += DEEP_BT) dst[i] = leaf_rec(d, i, 0);
+  for (int i = end + tid; i < n; i += DEEP_BT) put_leaf(dst, d, i, 0);
   if (tid == 0) lds_levels[t] = levels;
 }
 
@@ -420,6 +449,212 @@ __global__ void __launch_bounds__(DEEP_BT) score_forest_deep_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// attribution (docs/DESIGN.md §8): the deep walk with the taken edge's f32
+// delta added to acc[row][feat] along the path. BITWISE equal to
+// cpu_engine.feature_contributions, so a row's adds keep one order: trees
+// 0..T-1, root to leaf. A thread therefore walks the trees of a phase
+// strictly one after another and takes its independent chains from its RPT
+// rows (and the other resident waves), never from several trees of a row.
+//
+// Records ("explain deep" pack), int4 [Tpad][M]: x and y as above, z / w the
+// f32 bits of delta_left / delta_right; a leaf has threshold 0 and both
+// deltas +0.0. Per tree:
+//   phase A  lds_levels[t] fixed trips (the tree is block-uniform, so no
+//            minimum over the phase): one 128-bit LDS read of the record,
+//            the key read, the compare, the add, the step. A chain at a leaf
+//            self-loops and adds +0.0 (to column d when ACC_LDS).
+//   phase B  as in scoring, with 16-byte records; a finished chain adds
+//            nothing.
+// ACC_LDS: accumulators in a feature-major LDS tile [d + 1][FS] of f32: the
+// bank is the thread's own whatever feature a lane adds to, slab d absorbs
+// the self-loop adds; zeroed per row tile, flushed with coalesced stores.
+// Otherwise the pre-zeroed out[N][d] itself, thread-owned, the add
+// predicated on f < d and row < N, finalized in place. No atomics.
+// ---------------------------------------------------------------------------
+
+#define XDEEP_PH 4
+
+// correctly rounded f32 quotient: numpy's f32 divide bit for bit
+// (forest_kernels.hip, div32_exact)
+__device__ __forceinline__ float div32_exact(float a, float b) {
+  return (float)((double)a / (double)b);
+}
+
+template <typename KT, int RPT, bool ACC_LDS>
+__global__ void __launch_bounds__(DEEP_BT) explain_forest_deep_kernel(
+    const KT* __restrict__ X,               // raw bf16/fp16/f32 bits
+    const int4* __restrict__ nodes,         // [Tpad][M] explain deep records
+    const int32_t* __restrict__ lds_levels, // [Tpad]
+    float* __restrict__ out,                // [N][d] (pre-zeroed if !ACC_LDS)
+    int64_t N, int32_t d, int32_t Tpad, int32_t M, int32_t S, int32_t height,
+    float fT, int32_t finalize, int64_t rs, int64_t cs) {
+  constexpr int FS = RPT * DEEP_BT;
+  constexpr int PH = XDEEP_PH;
+  constexpr uint32_t ALL = (1u << RPT) - 1u;
+  const int tid = threadIdx.x;
+  const int staged = min(S, M);  // records of a tree that the stage holds
+
+  int4* tlds = (int4*)smem;              // [PH][S]
+  float* acc = (float*)(tlds + PH * S);  // [d + 1][FS] when ACC_LDS
+  KT* rows = (KT*)(acc + (ACC_LDS ? (d + 1) * FS : 0));
+
+  for (int64_t block_row0 = (int64_t)blockIdx.x * FS; block_row0 < N;
+       block_row0 += (int64_t)gridDim.x * FS) {
+    const int rows_here = (int)min((int64_t)FS, N - block_row0);
+
+    __syncthreads();  // previous tile's flush / readers done
+    stage_tile<KT, RPT>(rows, X, block_row0, rows_here, d, rs, cs);
+    if (ACC_LDS)
+      for (int i = tid; i < (d + 1) * FS; i += DEEP_BT) acc[i] = 0.f;
+    // the first phase's barriers order these stores before the walk
+
+    const KT* rb[RPT];
+    float* ab[RPT];     // ACC_LDS: the row's column 0 in the tile
+    int64_t ooff[RPT];  // else: the row's offset in out
+    bool inb[RPT];
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+      const int j = tid + r * DEEP_BT;
+      rb[r] = rows + tile_slot<KT, RPT>(j);
+      ab[r] = acc + j;
+      ooff[r] = (block_row0 + j) * d;
+      inb[r] = j < rows_here;
+    }
+
+    // adds delta[r] to the accumulator of (row r, feature f[r]) for every r
+    // in `on`: all reads before all writes (the rows' cells are distinct)
+    auto accumulate = [&](const int (&f)[RPT], const float (&delta)[RPT],
+                          uint32_t on) __attribute__((always_inline)) {
+      float a[RPT];
+      if (ACC_LDS) {
+#pragma unroll
+        for (int r = 0; r < RPT; ++r)
+          if (on & (1u << r)) a[r] = ab[r][f[r] * FS];
+#pragma unroll
+        for (int r = 0; r < RPT; ++r)
+          if (on & (1u << r)) ab[r][f[r] * FS] = __fadd_rn(a[r], delta[r]);
+      } else {
+        uint32_t ok = 0;
+#pragma unroll
+        for (int r = 0; r < RPT; ++r)
+          if ((on & (1u << r)) && f[r] < d && inb[r]) ok |= 1u << r;
+#pragma unroll
+        for (int r = 0; r < RPT; ++r)
+          if (ok & (1u << r)) a[r] = out[ooff[r] + f[r]];
+#pragma unroll
+        for (int r = 0; r < RPT; ++r)
+          if (ok & (1u << r)) out[ooff[r] + f[r]] = __fadd_rn(a[r], delta[r]);
+      }
+    };
+
+    for (int t = 0; t < Tpad; t += PH) {
+      __syncthreads();  // previous phase's LDS readers done
+#pragma unroll
+      for (int s = 0; s < PH; ++s) {
+        const int4* src = nodes + (int64_t)(t + s) * M;
+        int4* dst = tlds + s * S;
+        for (int i = tid; i < staged; i += DEEP_BT) dst[i] = src[i];
+      }
+      __syncthreads();
+
+#pragma unroll 1
+      for (int s = 0; s < PH; ++s) {  // a row's trees: strictly in order
+        const int4* ts = tlds + s * S;
+        const int4* nb = nodes + (int64_t)(t + s) * M;
+        const int la = min(lds_levels[t + s], height);
+        int cur[RPT];
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) cur[r] = 0;
+
+        // ---- phase A: la levels, LDS only ---------------------------------
+        for (int it = 0; it < la; ++it) {
+          int4 nd[RPT];
+#pragma unroll
+          for (int r = 0; r < RPT; ++r) nd[r] = ts[cur[r]];
+          int f[RPT];
+          KT kraw[RPT];
+#pragma unroll
+          for (int r = 0; r < RPT; ++r) {
+            f[r] = rec_feat(nd[r].x);
+            kraw[r] = rb[r][f[r] * FS];
+          }
+          float delta[RPT];
+#pragma unroll
+          for (int r = 0; r < RPT; ++r) {
+            const bool left = widen_key(kraw[r]) < (uint32_t)nd[r].y;
+            delta[r] = __int_as_float(left ? nd[r].z : nd[r].w);
+            cur[r] = rec_link(nd[r].x) - (int)left;
+          }
+          accumulate(f, delta, ALL);
+        }
+
+        // ---- phase B: the tail ---------------------------------------------
+        // bit r of `live`: the chain has not read its leaf yet. `first`: see
+        // score_forest_deep_kernel
+        uint32_t live = ALL;
+        auto tail_trip = [&](auto first) __attribute__((always_inline)) {
+          int4 nd[RPT];
+#pragma unroll
+          for (int r = 0; r < RPT; ++r)
+            if (live & (1u << r)) {
+              if (decltype(first)::value && cur[r] < S)
+                nd[r] = ts[cur[r]];
+              else
+                nd[r] = nb[cur[r]];
+            }
+          int f[RPT];
+          KT kraw[RPT];
+#pragma unroll
+          for (int r = 0; r < RPT; ++r)
+            if (live & (1u << r)) {
+              f[r] = rec_feat(nd[r].x);
+              kraw[r] = rb[r][f[r] * FS];
+            }
+          float delta[RPT];
+#pragma unroll
+          for (int r = 0; r < RPT; ++r)
+            if (live & (1u << r)) {
+              const int link = rec_link(nd[r].x);
+              if (link == cur[r]) {
+                live &= ~(1u << r);
+              } else {
+                const bool left = widen_key(kraw[r]) < (uint32_t)nd[r].y;
+                delta[r] = __int_as_float(left ? nd[r].z : nd[r].w);
+                cur[r] = link - (int)left;
+              }
+            }
+          // a chain that has read its leaf adds nothing
+          accumulate(f, delta, live);
+        };
+        tail_trip(std::true_type{});
+        // a chain at depth `height` is a leaf: height - la more trips read it
+        for (int k = la; k < height && __any(live != 0); ++k)
+          tail_trip(std::false_type{});
+      }
+    }
+
+    if (ACC_LDS) {
+      __syncthreads();  // every row's accumulators final
+      const int total = rows_here * d;
+      float* o = out + block_row0 * d;
+      for (int g = tid; g < total; g += DEEP_BT) {
+        const int r = (int)((uint32_t)g / (uint32_t)d), c = g - r * d;
+        const float v = acc[c * FS + r];
+        o[g] = finalize ? div32_exact(v, fT) : v;
+      }
+    } else if (finalize) {
+#pragma unroll
+      for (int r = 0; r < RPT; ++r)
+        if (inb[r])
+          for (int c = 0; c < d; ++c) {
+            float* o = out + ooff[r] + c;
+            *o = div32_exact(*o, fT);
+          }
+    }
+  }
+}
+
 }  // namespace deep
 
 // host-side launchers (bindings.cpp is compiled by g++)
@@ -430,9 +665,21 @@ void launch_deep_level_order(const int32_t* feat, const int32_t* right,
                              int32_t* lds_levels, int32_t T, int32_t Tpad,
                              int32_t M0, int32_t M, int32_t S, int32_t d,
                              hipStream_t stream) {
-  hipLaunchKernelGGL(deep::deep_level_order_kernel, dim3(Tpad), dim3(DEEP_BT),
-                     0, stream, feat, right, w, ncount, front_a, front_b,
-                     (int2*)out, lds_levels, T, M0, M, S, d);
+  hipLaunchKernelGGL(deep::deep_level_order_kernel<int2>, dim3(Tpad),
+                     dim3(DEEP_BT), 0, stream, feat, right, w,
+                     (const int32_t*)nullptr, (const int32_t*)nullptr, ncount,
+                     front_a, front_b, (int2*)out, lds_levels, T, M0, M, S, d);
+}
+
+void launch_explain_deep_level_order(
+    const int32_t* feat, const int32_t* right, const int32_t* w,
+    const int32_t* dl, const int32_t* dr, const int32_t* ncount,
+    uint32_t* front_a, uint32_t* front_b, void* out, int32_t* lds_levels,
+    int32_t T, int32_t Tpad, int32_t M0, int32_t M, int32_t S, int32_t d,
+    hipStream_t stream) {
+  hipLaunchKernelGGL(deep::deep_level_order_kernel<int4>, dim3(Tpad),
+                     dim3(DEEP_BT), 0, stream, feat, right, w, dl, dr, ncount,
+                     front_a, front_b, (int4*)out, lds_levels, T, M0, M, S, d);
 }
 
 hipError_t launch_score_forest_deep(RowDtype dt, int rpt, const void* X,
@@ -466,6 +713,45 @@ hipError_t launch_score_forest_deep(RowDtype dt, int rpt, const void* X,
   else LDP(uint32_t);
 #undef LDP
 #undef LDP1
+  return hipGetLastError();
+}
+
+hipError_t launch_explain_forest_deep(RowDtype dt, int rpt, bool acc_lds,
+                                      const void* X, const void* nodes,
+                                      const int32_t* lds_levels, float* out,
+                                      int64_t N, int32_t d, int64_t rs,
+                                      int64_t cs, int32_t Tpad, int32_t M,
+                                      int32_t S, int32_t height, float fT,
+                                      int finalize, size_t lds, int blocks,
+                                      hipStream_t stream) {
+  // the binding's two shapes: two rows a thread with the accumulator tile,
+  // one row a thread with the accumulators in out
+  if ((rpt != 2 || !acc_lds) && (rpt != 1 || acc_lds))
+    return hipErrorInvalidValue;
+  hipError_t err = hipSuccess;
+#define LXD1(KT, RPT, AL)                                                     \
+  do {                                                                        \
+    const void* fn =                                                          \
+        (const void*)deep::explain_forest_deep_kernel<KT, RPT, AL>;           \
+    if (lds > 64 * 1024)                                                      \
+      err = hipFuncSetAttribute(                                              \
+          fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
+    if (err != hipSuccess) return err;                                        \
+    hipLaunchKernelGGL((deep::explain_forest_deep_kernel<KT, RPT, AL>),       \
+                       dim3(blocks), dim3(DEEP_BT), lds, stream,              \
+                       (const KT*)X, (const int4*)nodes, lds_levels, out, N,  \
+                       d, Tpad, M, S, height, fT, finalize, rs, cs);          \
+  } while (0)
+#define LXD(KT)                                                               \
+  do {                                                                        \
+    if (acc_lds) LXD1(KT, 2, true);                                           \
+    else LXD1(KT, 1, false);                                                  \
+  } while (0)
+  if (dt == ROW_BF16) LXD(uint16_t);
+  else if (dt == ROW_F16) LXD(deep::f16_t);
+  else LXD(uint32_t);
+#undef LXD
+#undef LXD1
   return hipGetLastError();
 }
 
