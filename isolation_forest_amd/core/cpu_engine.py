@@ -726,6 +726,33 @@ def edge_deltas(forest, E: np.ndarray = None):
     return dl, dr
 
 
+def _extended_shares(feature, hyper_w, dl64, dr64):
+    """explain_tables' EIF shares: the float64 edge deltas [T, m] spread over
+    the k = feature[t, v] hyperplane coordinates in proportion to w_j^2,
+    rounded once to float32 [T, m, nnz]. Element-wise per node, so a column
+    slice of the arrays gives that slice of the result."""
+    nnz = hyper_w.shape[2]
+    k = np.where(feature >= 0, feature, 0).astype(np.int64)
+    used = np.arange(nnz, dtype=np.int64)[None, None, :] < k[:, :, None]
+    w = hyper_w.astype(np.float64)
+    sq = np.where(used, w * w, 0.0)
+    tot = np.zeros(k.shape, dtype=np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for j in range(nnz):  # ascending j, like every other EIF sum
+            tot = tot + sq[:, :, j]
+    ok = np.isfinite(tot) & (tot > 0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        share = np.where(
+            ok[:, :, None], sq / np.where(ok, tot, 1.0)[:, :, None],
+            1.0 / np.maximum(k, 1)[:, :, None].astype(np.float64))
+    share = np.where(used, share, 0.0)
+    dl = (dl64[:, :, None] * share).astype(np.float32)
+    dr = (dr64[:, :, None] * share).astype(np.float32)
+    dl[~used] = 0.0
+    dr[~used] = 0.0
+    return dl, dr
+
+
 def explain_tables(forest):
     """Cached per-forest attribution tables (forests are immutable):
     ``bias`` = f32(mean_t E[root_t]) and float32 edge deltas. Standard:
@@ -747,25 +774,7 @@ def explain_tables(forest):
     bias = (np.float32(E[:, 0].mean()) if forest.num_trees
             else np.float32(0.0))
     if isinstance(forest, ExtendedForest):
-        nnz = forest.nnz
-        k = np.where(forest.feature >= 0, forest.feature, 0).astype(np.int64)
-        used = np.arange(nnz, dtype=np.int64)[None, None, :] < k[:, :, None]
-        w = forest.hyper_w.astype(np.float64)
-        sq = np.where(used, w * w, 0.0)
-        tot = np.zeros(k.shape, dtype=np.float64)
-        with np.errstate(over="ignore", invalid="ignore"):
-            for j in range(nnz):  # ascending j, like every other EIF sum
-                tot = tot + sq[:, :, j]
-        ok = np.isfinite(tot) & (tot > 0)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            share = np.where(
-                ok[:, :, None], sq / np.where(ok, tot, 1.0)[:, :, None],
-                1.0 / np.maximum(k, 1)[:, :, None].astype(np.float64))
-        share = np.where(used, share, 0.0)
-        dl = (dl64[:, :, None] * share).astype(np.float32)
-        dr = (dr64[:, :, None] * share).astype(np.float32)
-        dl[~used] = 0.0
-        dr[~used] = 0.0
+        dl, dr = _extended_shares(forest.feature, forest.hyper_w, dl64, dr64)
     else:
         dl = dl64.astype(np.float32)
         dr = dr64.astype(np.float32)
@@ -776,13 +785,14 @@ def explain_tables(forest):
 
 
 def explain_tables_trimmed(forest):
-    """explain_tables of a standard forest over its first
-    M = max(node_count) columns only: ``bias`` and float32 ``dl``/``dr``
-    [T, M], bit for bit explain_tables' first M columns (pre-order keeps
-    every child of a live node below node_count, so the sweep never looks
-    past them). For forests whose arrays are far wider than their trees
-    (2n - 1 columns, a few thousand nodes): no [T, 2n - 1] float64
-    temporaries. Not cached; the device pack that uses it is."""
+    """explain_tables over the forest's first M = max(node_count) columns
+    only: ``bias`` and float32 ``dl``/``dr`` [T, M] ([T, M, nnz] for an
+    extended forest), bit for bit explain_tables' first M columns (pre-order
+    keeps every child of a live node below node_count, so the sweep never
+    looks past them, and the EIF shares are computed node by node). For
+    forests whose arrays are far wider than their trees (2n - 1 or
+    2^(H+1) - 1 columns): no float64 temporaries of the full width. Not
+    cached; the device pack that uses it is."""
     import types
 
     m = max(int(np.max(forest.node_count, initial=1)), 1)
@@ -795,9 +805,13 @@ def explain_tables_trimmed(forest):
     dl64, dr64 = edge_deltas(trimmed, E)
     bias = (np.float32(E[:, 0].mean()) if forest.num_trees
             else np.float32(0.0))
-    return {"bias": bias,
-            "dl": np.ascontiguousarray(dl64.astype(np.float32)),
-            "dr": np.ascontiguousarray(dr64.astype(np.float32))}
+    if isinstance(forest, ExtendedForest):
+        dl, dr = _extended_shares(trimmed.feature, forest.hyper_w[:, :m],
+                                  dl64, dr64)
+    else:
+        dl, dr = dl64.astype(np.float32), dr64.astype(np.float32)
+    return {"bias": bias, "dl": np.ascontiguousarray(dl),
+            "dr": np.ascontiguousarray(dr)}
 
 
 def expected_path_length(forest) -> np.float32:

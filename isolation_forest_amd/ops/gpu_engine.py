@@ -814,6 +814,35 @@ def _nodes_explain_deep_host(forest, kind):
             np.ascontiguousarray(tabs["dr"]).view(np.int32), nc, max_depth)
 
 
+def _nodes_explain_eif_deep_host(forest):
+    """Host half of the explain eif deep pack (ops/hip/deep_kernels.hip):
+    the pre-order arrays of an extended forest TRIMMED to the largest
+    node_count. int32 [T, M0]: the coordinate count k of an internal node
+    (-1 for leaves and dead slots), the pre-order right child, the f32 bits
+    of the offset; int32 [T, M0, nnz]: the coordinates and the f32 bits of
+    the weights and of the two edges' shares, from
+    cpu_engine.explain_tables_trimmed — the CPU oracle's shares without its
+    [T, 2^(H+1) - 1, nnz] float64 sweep. Returns (feat, right, w,
+    node_count, hidx, hw, dl, dr, max_depth)."""
+    from ..core.cpu_engine import explain_tables_trimmed
+
+    nc = np.ascontiguousarray(forest.node_count, dtype=np.int32)
+    m0 = max(int(nc.max(initial=1)), 1)
+    feat = np.ascontiguousarray(forest.feature[:, :m0])
+    right = np.ascontiguousarray(forest.right[:, :m0], dtype=np.int32)
+    internal = feat >= 0
+    live = internal | (feat == ExtendedForest.LEAF)
+    depth = _node_depths(feat, right)
+    max_depth = int(depth[live].max()) if live.any() else 0
+    tabs = explain_tables_trimmed(forest)
+    bits = lambda a: np.ascontiguousarray(a, dtype=np.float32).view(np.int32)  # noqa: E731
+    return (np.where(internal, feat, -1).astype(np.int32), right,
+            bits(forest.value[:, :m0]), nc,
+            np.ascontiguousarray(forest.hyper_idx[:, :m0], dtype=np.int32),
+            bits(forest.hyper_w[:, :m0]), bits(tabs["dl"]), bits(tabs["dr"]),
+            max(max_depth, 1))
+
+
 def _nodes_packed_explain(forest, d_sentinel: int, bf16):
     """16-byte node records for explain_forest_kernel (`bf16` is the row
     kind, as in _nodes_packed_v4):
@@ -1358,9 +1387,11 @@ def _device_forest(model, device, v4_key=None):
     ("explain_deep", d, stage, kind), ("shap", d, kind) — are keyed
     on the row KIND, not on "is it 16-bit": bf16 and fp16 keys differ, and
     u32 records under a u16 kernel score silently wrong. The "shap" entry
-    is (table words, per-tree word offsets, {host offsets, weights})."""
-    if isinstance(v4_key, tuple) and v4_key[0] not in ("eif_dense",
-                                                       "eif_dense3"):
+    is (table words, per-tree word offsets, {host offsets, weights}).
+    ("explain_eif_deep", stage) holds f32 offsets and weights and serves
+    every row kind."""
+    if isinstance(v4_key, tuple) and v4_key[0] not in (
+            "eif_dense", "eif_dense3", "explain_eif_deep"):
         v4_key = v4_key[:-1] + (_row_kind(v4_key[-1]),)
     key = (str(device), id(model.forest), v4_key)
     cache = model._gpu_forest_cache
@@ -1511,6 +1542,18 @@ def _device_forest(model, device, v4_key=None):
                 *(torch.from_numpy(a).to(device)
                   for a in (feat, right, w, dl, dr, nc)),
                 v4_key[1], v4_key[2])
+            extra["height"] = max_depth
+        elif isinstance(v4_key, tuple) and v4_key[0] == "explain_eif_deep":
+            # ("explain_eif_deep", stage): aos = the level-order node
+            # records, ncount = lds_levels, extra["payload"] = the
+            # per-coordinate entries, all made on the device
+            from . import load_extension as _packing_extension
+
+            *arrays, max_depth = _nodes_explain_eif_deep_host(forest)
+            aos, extra["payload"], ncount = \
+                _packing_extension().explain_eif_deep_pack(
+                    *(torch.from_numpy(a).to(device) for a in arrays),
+                    max(_coord_range(forest)[1], 0) + 1, v4_key[1])
             extra["height"] = max_depth
         elif v4_key == "eif_wide":
             packed = _eif_packed_wide(forest)
@@ -1767,15 +1810,49 @@ def _explain_deep_stage(kind: str, d: int) -> int:
     return int(_packing_extension().explain_deep_stage(kind, int(d)))
 
 
+def _explain_eif_deep_stage(kind: str, d: int, nnz: int) -> int:
+    """Node records per tree the deep EIF explain walk stages for these rows
+    and this hyperplane width now (0: the tiles leave no room); see
+    _deep_stage."""
+    from . import load_extension as _packing_extension
+
+    return int(_packing_extension().explain_eif_deep_stage(
+        kind, int(d), int(nnz)))
+
+
+def _coord_range(forest):
+    """(smallest, largest) hyperplane coordinate over the internal nodes of
+    an extended forest, (0, -1) for a forest of leaves; cached on the forest
+    like _feature_max: a pass over [T, 2^(H+1) - 1, nnz], made once."""
+    rng = getattr(forest, "_coord_range", None)
+    if rng is None:
+        internal = forest.feature >= 0
+        rng = (0, -1)
+        if internal.any():
+            idx = forest.hyper_idx[internal]
+            rng = (int(idx.min()), int(idx.max()))
+        forest._coord_range = rng
+    return rng
+
+
 def large_explain_route(forest, d: int, dtype) -> str:
-    """Where ``explain_forest`` attributes a forest past the packed 15-bit
-    node ids: ``"deep"`` (explain_forest_deep: 16-byte level-order records,
-    top levels in LDS, tail from L2) or ``"cpu"`` (the oracle, with a logged
-    warning). ``IFA_EXPLAIN_DEEP=0`` keeps the CPU path; so do extended
-    forests, forests past ``DEEP_MAX_NODES`` nodes a tree or 4094 features,
-    and rows too wide for the key tile to leave a stage in LDS."""
+    """Where ``explain_forest`` and ``explain_extended_forest`` attribute a
+    forest past the packed 15-bit node ids: ``"deep"`` (explain_forest_deep /
+    explain_extended_deep: level-order records, top levels in LDS, tail from
+    L2) or ``"cpu"`` (the oracle, with a logged warning).
+    ``IFA_EXPLAIN_DEEP=0`` keeps the CPU path; so do forests past
+    ``DEEP_MAX_NODES`` nodes a tree or 4094 features (extended: coordinates,
+    hyperplane widths), and rows too wide for the tiles to leave a stage in
+    LDS."""
     if os.environ.get("IFA_EXPLAIN_DEEP", "1") == "0":
         return "cpu"
+    if isinstance(forest, ExtendedForest):
+        if int(np.max(forest.node_count, initial=1)) > DEEP_MAX_NODES:
+            return "cpu"
+        if max(_coord_range(forest)[1], d, forest.nnz) > 4094:
+            return "cpu"
+        stage = _explain_eif_deep_stage(_row_kind(dtype), d, forest.nnz)
+        return "deep" if stage > 0 else "cpu"
     if not _deep_fits(forest, d):
         return "cpu"
     return "deep" if _explain_deep_stage(_row_kind(dtype), d) > 0 else "cpu"
@@ -1835,19 +1912,26 @@ def explain_extended_forest(model, X: torch.Tensor,
                             finalize: bool = True) -> torch.Tensor:
     """EIF contributions [N, d] float32 on X's device, bitwise equal to
     cpu_engine.feature_contributions_extended at every extension level
-    (one strict-order kernel, no routing)."""
+    (one strict-order kernel for forests inside the packed caps; past them
+    explain_extended_deep, see large_explain_route)."""
     from ..core import cpu_engine
 
     forest = model.forest
     d = int(X.shape[1])
     _check_explain_input(X)
-    internal = forest.feature >= 0
-    cmax = (int(forest.hyper_idx[internal].max(initial=-1))
-            if internal.any() else -1)
+    cmin, cmax = _coord_range(forest)
     if cmax >= d:
         raise ValueError(
             f"the forest splits on feature {cmax} but rows have {d} columns")
     if not _packed_fits(forest, d):
+        kind = _row_kind(X.dtype)
+        if cmin >= 0 and large_explain_route(forest, d, kind) == "deep":
+            stage = _explain_eif_deep_stage(kind, d, forest.nnz)
+            nodes, lds_levels, extra = _device_forest(
+                model, X.device, v4_key=("explain_eif_deep", stage))
+            return load_extension().explain_extended_deep(
+                _rows_in_place(X), nodes, extra["payload"], lds_levels,
+                forest.num_trees, extra["height"], stage, finalize)
         return _explain_on_cpu(
             cpu_engine.feature_contributions_extended, forest, X, finalize,
             "forest exceeds the packed node format (15-bit node ids, "

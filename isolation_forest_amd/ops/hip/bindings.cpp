@@ -218,6 +218,17 @@ hipError_t launch_explain_forest_deep(RowDtype dt, int rpt, bool acc_lds,
                                       int32_t S, int32_t height, float fT,
                                       int finalize, size_t lds, int blocks,
                                       hipStream_t stream);
+void launch_eif_deep_gather(const void* lvl, const int32_t* hidx,
+                            const int32_t* hw, const int32_t* dl,
+                            const int32_t* dr, void* nodes, void* payload,
+                            int32_t T, int32_t Tpad, int32_t M0, int32_t M,
+                            int32_t nnz, int32_t d, hipStream_t stream);
+hipError_t launch_explain_extended_deep(
+    RowDtype dt, int rpt, bool acc_lds, const void* X, const void* nodes,
+    const void* payload, const int32_t* lds_levels, float* out, int64_t N,
+    int32_t d, int32_t nnz, int64_t rs, int64_t cs, int32_t Tpad, int32_t M,
+    int32_t S, int32_t trees_per_phase, int32_t height, float fT, int finalize,
+    size_t lds, int blocks, hipStream_t stream);
 
 // bag_kernels.hip
 int launch_bag_sample_lds(int64_t* out, int32_t* err, uint64_t seed,
@@ -1586,6 +1597,206 @@ torch::Tensor explain_forest_deep(torch::Tensor X, torch::Tensor records,
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// attribution for extended forests past the packed caps
+// (explain_extended_deep_kernel): 8-byte level-order node records and a
+// 16-byte payload entry per hyperplane coordinate
+// ---------------------------------------------------------------------------
+
+constexpr int kEDeepStage = 1024;   // most records staged per tree
+constexpr int kEDeepMinStage = 16;  // least, while a smaller LDS share or
+                                    // the accumulator tile is still a choice
+
+struct ExplainEifDeepCfg {
+  int rpt, stage, trees;  // stage 0: the tiles leave no room for a stage
+  bool acc_lds;
+  size_t lds;
+};
+
+// The stage S, the trees per barrier phase and the accumulator route from the
+// LDS left beside the tiles. A staged node costs 8 + 16 * nnz bytes, so S is
+// what the hyperplane width allows: the largest power of two up to
+// kEDeepStage, then as many trees a phase (4, 2, 1) as still fit. The order
+// of the shapes is pick_explain_deep_cfg's (profiles/explain_eif_deep.md):
+//  1. two rows a thread with the f32 accumulator tile [d][512] in LDS, two
+//     blocks resident per CU, then one;
+//  2. the tile does not fit, or IFA_EXPLAIN_FORCE_GLOBAL_ACC=1: the adds go
+//     to out[N, d] itself at one row a thread.
+// The last shape tried goes down to S = 2. IFA_EXPLAIN_DEEP_STAGE=<records>
+// forces S to any power of two >= 2; a forced S that fits neither route
+// leaves none.
+ExplainEifDeepCfg pick_explain_eif_deep_cfg(int elem_bytes, int64_t d,
+                                            int64_t nnz) {
+  int forced = 0;
+  if (const char* e = getenv("IFA_EXPLAIN_DEEP_STAGE")) {
+    const long v = atol(e);
+    if (v >= 2 && v <= kDeepMaxNodes && (v & (v - 1)) == 0) forced = (int)v;
+  }
+  bool force_global = false;
+  if (const char* e = getenv("IFA_EXPLAIN_FORCE_GLOBAL_ACC"))
+    force_global = atoi(e) != 0;
+  const size_t node = 8 + 16 * (size_t)nnz;
+  const size_t one_block = (size_t)150 * 1024;
+  auto fit = [&](int rpt, bool acc_lds, size_t tiles, size_t budget,
+                 int s_lo) -> ExplainEifDeepCfg {
+    for (int s = forced ? forced : kEDeepStage; s >= (forced ? forced : s_lo);
+         s >>= 1)
+      for (int trees : {4, 2, 1}) {
+        const size_t l = tiles + (size_t)trees * s * node;
+        if (l <= budget) return {rpt, s, trees, acc_lds, l};
+      }
+    return {0, 0, 0, false, 0};
+  };
+  if (!force_global) {
+    const size_t tiles = (size_t)2 * 256 * d * ((size_t)elem_bytes + 4);
+    for (size_t budget : {kMaxLds / 2, one_block}) {
+      const ExplainEifDeepCfg c = fit(2, true, tiles, budget, kEDeepMinStage);
+      if (c.stage) return c;
+    }
+  }
+  return fit(1, false, (size_t)256 * d * (size_t)elem_bytes, one_block, 2);
+}
+
+// the stage explain_extended_deep runs rows of this kind and width with now
+// for hyperplanes of nnz coordinates, or 0 where it has no route for them
+int64_t explain_eif_deep_stage(const std::string& dtype, int64_t d,
+                               int64_t nnz) {
+  if (d < 1 || d > 4094 || nnz < 1 || nnz > 4094) return 0;
+  return pick_explain_eif_deep_cfg(elem_bytes_of(dtype), d, nnz).stage;
+}
+
+// Trimmed pre-order arrays of an extended forest -> the explain eif deep
+// pack for a stage of `stage`: node records int32 [Tpad, M, 2], payload
+// int32 [Tpad, M, nnz, 4] and lds_levels int32 [Tpad]. feat [T, M0] is the
+// coordinate count k of an internal node (< 0: leaf), w the f32 bits of its
+// offset; hidx, hw, dl and dr [T, M0, nnz] are the coordinates and the f32
+// bits of weights and edge shares. The level order is
+// deep_level_order_kernel<int4>'s, run with every slot's own pre-order index
+// in place of delta_left; the gather then moves each node's payload to its
+// new slot. Coordinates are clamped to [0, coord_cap).
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> explain_eif_deep_pack(
+    torch::Tensor feat, torch::Tensor right, torch::Tensor w,
+    torch::Tensor ncount, torch::Tensor hidx, torch::Tensor hw,
+    torch::Tensor dl, torch::Tensor dr, int64_t coord_cap, int64_t stage) {
+  for (const torch::Tensor* a : {&feat, &right, &w}) {
+    CHECK_CUDA(*a);
+    CHECK_CONTIG(*a);
+    TORCH_CHECK(a->dim() == 2 && a->scalar_type() == torch::kInt32 &&
+                    a->sizes() == feat.sizes(),
+                "feat, right and w must be int32 [T, M0]");
+  }
+  const int64_t T = feat.size(0), M0 = feat.size(1);
+  for (const torch::Tensor* a : {&hidx, &hw, &dl, &dr}) {
+    CHECK_CUDA(*a);
+    CHECK_CONTIG(*a);
+    TORCH_CHECK(a->dim() == 3 && a->scalar_type() == torch::kInt32 &&
+                    a->sizes() == hidx.sizes() && a->size(0) == T &&
+                    a->size(1) == M0,
+                "hidx, hw, dl and dr must be int32 [T, M0, nnz]");
+  }
+  CHECK_CUDA(ncount);
+  CHECK_CONTIG(ncount);
+  TORCH_CHECK(ncount.scalar_type() == torch::kInt32 && ncount.dim() == 1 &&
+                  ncount.size(0) == T,
+              "ncount must be int32 [T]");
+  const int64_t nnz = hidx.size(2);
+  TORCH_CHECK(M0 >= 1 && M0 <= kDeepMaxNodes, "deep links are 20 bits");
+  TORCH_CHECK(nnz >= 1 && nnz <= 4094 && coord_cap >= 1 && coord_cap <= 4094,
+              "hyperplane widths and coordinates are 12 bits");
+  TORCH_CHECK(stage >= 2 && stage <= kDeepMaxNodes &&
+                  (stage & (stage - 1)) == 0,
+              "stage must be a power of two >= 2");
+  TORCH_CHECK(T <= 65535 * kDeepPhase, "too many trees");
+  const int64_t Tpad = (T + kDeepPhase - 1) / kDeepPhase * kDeepPhase;
+  const int64_t M = M0;
+  auto nodes = torch::empty({Tpad, M, 2}, feat.options());
+  auto payload = torch::empty({Tpad, M, nnz, 4}, feat.options());
+  auto levels = torch::empty({Tpad}, feat.options());
+  if (T == 0) return {nodes, payload, levels};
+  auto lvl = torch::empty({Tpad, M, 4}, feat.options());
+  auto old = torch::arange(M0, feat.options()).expand({T, M0}).contiguous();
+  auto front = torch::empty({2, T, M0}, feat.options());
+  int32_t* fr = front.data_ptr<int32_t>();
+  // leaf sentinel 0: a leaf record is k = 0 with a link to itself
+  ifa::launch_explain_deep_level_order(
+      feat.data_ptr<int32_t>(), right.data_ptr<int32_t>(),
+      w.data_ptr<int32_t>(), old.data_ptr<int32_t>(), old.data_ptr<int32_t>(),
+      ncount.data_ptr<int32_t>(), (uint32_t*)fr, (uint32_t*)(fr + T * M0),
+      lvl.data_ptr<int32_t>(), levels.data_ptr<int32_t>(), (int32_t)T,
+      (int32_t)Tpad, (int32_t)M0, (int32_t)M, (int32_t)stage, 0,
+      current_stream());
+  ifa::launch_eif_deep_gather(
+      lvl.data_ptr<int32_t>(), hidx.data_ptr<int32_t>(),
+      hw.data_ptr<int32_t>(), dl.data_ptr<int32_t>(), dr.data_ptr<int32_t>(),
+      nodes.data_ptr<int32_t>(), payload.data_ptr<int32_t>(), (int32_t)T,
+      (int32_t)Tpad, (int32_t)M0, (int32_t)M, (int32_t)nnz,
+      (int32_t)coord_cap, current_stream());
+  return {nodes, payload, levels};
+}
+
+// Returns the f32 [N, d] contribution matrix (raw sums when !finalize).
+// `stage` is the one the pack's lds_levels were counted for.
+torch::Tensor explain_extended_deep(torch::Tensor X, torch::Tensor nodes,
+                                    torch::Tensor payload,
+                                    torch::Tensor lds_levels,
+                                    int64_t num_trees, int64_t height,
+                                    int64_t stage, bool finalize) {
+  CHECK_CUDA(X);
+  for (const torch::Tensor* a : {&nodes, &payload, &lds_levels}) {
+    CHECK_CUDA(*a);
+    CHECK_CONTIG(*a);
+    TORCH_CHECK(a->scalar_type() == torch::kInt32, "the pack is int32");
+  }
+  check_x(X);
+  const XLayout xl = check_x_layout(X);
+  TORCH_CHECK(nodes.dim() == 3 && nodes.size(2) == 2,
+              "nodes must be int32 [Tpad, M, 2]");
+  const int64_t N = X.size(0), d = X.size(1);
+  const int64_t Tpad = nodes.size(0), M = nodes.size(1);
+  TORCH_CHECK(payload.dim() == 4 && payload.size(0) == Tpad &&
+                  payload.size(1) == M && payload.size(3) == 4,
+              "payload must be int32 [Tpad, M, nnz, 4]");
+  const int64_t nnz = payload.size(2);
+  TORCH_CHECK(Tpad % kDeepPhase == 0 && num_trees >= 1 && num_trees <= Tpad,
+              "deep tree count must be padded to the phase");
+  TORCH_CHECK(M >= 1 && M <= kDeepMaxNodes,
+              "deep records hold at most 2^20 nodes a tree");
+  TORCH_CHECK(lds_levels.dim() == 1 && lds_levels.size(0) == Tpad,
+              "lds_levels must be int32 [Tpad]");
+  TORCH_CHECK(d >= 1 && d <= 4094 && nnz >= 1 && nnz <= 4094,
+              "explain supports 1 <= d, nnz <= 4094 (12-bit fields)");
+  TORCH_CHECK(height >= 1 && height <= 64, "height out of range");
+  const ifa::RowDtype dt = row_dtype(X);
+  const ExplainEifDeepCfg cfg =
+      pick_explain_eif_deep_cfg(ifa::row_elem_bytes(dt), d, nnz);
+  TORCH_CHECK(cfg.stage > 0 && cfg.stage == stage,
+              "the pack was staged for ", stage, " records a tree, rows of "
+              "this kind and width run ", cfg.stage);
+  const auto out_opts = X.options().dtype(torch::kFloat32);
+  // the LDS-tile flush writes every cell; the global route adds into out
+  auto out = cfg.acc_lds ? torch::empty({N, d}, out_opts)
+                         : torch::zeros({N, d}, out_opts);
+  if (N == 0) return out;
+  int64_t max_blocks = 8192;
+  if (const char* e = getenv("IFA_EXPLAIN_MAX_BLOCKS")) {
+    const int64_t v = atoll(e);
+    if (v >= 1) max_blocks = std::min<int64_t>(v, 8192);
+  }
+  const int64_t rows_per_block = (int64_t)cfg.rpt * 256;
+  const int blocks = (int)std::min<int64_t>(
+      (N + rows_per_block - 1) / rows_per_block, max_blocks);
+  const hipError_t err = ifa::launch_explain_extended_deep(
+      dt, cfg.rpt, cfg.acc_lds, X.data_ptr(), nodes.data_ptr<int32_t>(),
+      payload.data_ptr<int32_t>(), lds_levels.data_ptr<int32_t>(),
+      out.data_ptr<float>(), N, (int32_t)d, (int32_t)nnz, xl.rs, xl.cs,
+      (int32_t)Tpad, (int32_t)M, (int32_t)cfg.stage, (int32_t)cfg.trees,
+      (int32_t)height, (float)num_trees, finalize ? 1 : 0, cfg.lds, blocks,
+      current_stream());
+  TORCH_CHECK(err == hipSuccess, "explain_extended_deep launch failed (",
+              cfg.lds, " B of LDS): ", hipGetErrorString(err));
+  return out;
+}
+
 torch::Tensor score_extended_wide(torch::Tensor X, torch::Tensor nodes_wide,
                                   torch::Tensor hidx, torch::Tensor hw,
                                   double c_norm, bool finalize) {
@@ -1946,5 +2157,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "lds_levels");
   m.def("explain_forest_deep", &explain_forest_deep,
         "attribution past 15-bit node ids: LDS top levels, L2 tail");
+  m.def("explain_eif_deep_stage", &explain_eif_deep_stage,
+        "records per tree explain_extended_deep stages for (dtype, d, nnz); "
+        "0: none");
+  m.def("explain_eif_deep_pack", &explain_eif_deep_pack,
+        "trimmed pre-order extended forest -> level-order node records, "
+        "per-coordinate payload, lds_levels");
+  m.def("explain_extended_deep", &explain_extended_deep,
+        "EIF attribution past 15-bit node ids: LDS top levels, L2 tail");
   m.attr("WAVE") = 64;
 }

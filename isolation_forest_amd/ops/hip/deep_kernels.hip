@@ -45,6 +45,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "row_dtype.h"
@@ -256,8 +257,10 @@ __device__ __forceinline__ int tile_slot(int j) {
   return (j % P) * 2 + j / P;
 }
 
-// every thread keys its own rows into the tile; barriers are the caller's
-template <typename KT, int RPT>
+// every thread keys its own rows into the tile; barriers are the caller's.
+// !KEYS (the extended walk): the raw bits are stored, rows past N are +0.0
+// and there is no sentinel slab.
+template <typename KT, int RPT, bool KEYS = true>
 __device__ __forceinline__ void stage_tile(KT* rows, const KT* __restrict__ X,
                                            int64_t block_row0, int rows_here,
                                            int32_t d, int64_t rs, int64_t cs) {
@@ -278,17 +281,18 @@ __device__ __forceinline__ void stage_tile(KT* rows, const KT* __restrict__ X,
           pc.v = *(const uint4*)(src + c);
 #pragma unroll
           for (int k = 0; k < EPV; ++k)
-            dst[(c + k) * FS] = key_of_bits<KT>(pc.e[k]);
+            dst[(c + k) * FS] = KEYS ? key_of_bits<KT>(pc.e[k]) : pc.e[k];
         }
       } else {
         for (int c = 0; c < d; ++c, src += cs)
-          dst[c * FS] = key_of_bits<KT>(*src);
+          dst[c * FS] = KEYS ? key_of_bits<KT>(*src) : *src;
       }
     } else {
       // tail block: rows past N are walked but never stored
-      for (int c = 0; c < d; ++c) dst[c * FS] = key_sentinel<KT>();
+      for (int c = 0; c < d; ++c)
+        dst[c * FS] = KEYS ? key_sentinel<KT>() : (KT)0;
     }
-    dst[d * FS] = key_sentinel<KT>();  // leaf sentinel slab
+    if (KEYS) dst[d * FS] = key_sentinel<KT>();  // leaf sentinel slab
   }
 }
 
@@ -655,6 +659,270 @@ __global__ void __launch_bounds__(DEEP_BT) explain_forest_deep_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// extended forests (docs/DESIGN.md §8): the same two-phase walk over
+// hyperplane nodes. BITWISE equal to cpu_engine.feature_contributions_extended:
+// the dot is fadd(dot, fmul(w_j, x_j)) in ascending j from 0.f over all nnz
+// stored coordinates of an internal node (no FMA), the decision is
+// dot < offset (NaN goes right), and the taken edge's per-coordinate shares
+// are added in ascending j over the node's k coordinates, trees 0..T-1, root
+// to leaf. Coordinates of a node may repeat: a row's adds of one visit are
+// read-add-write one after another.
+//
+// Pack ("explain eif deep"), level order as above:
+//   nodes    int2 [Tpad][M]       x = k | link << 12, y = f32 bits of offset;
+//                                 a leaf has link = its own index and k = 0
+//   payload  int4 [Tpad][M][nnz]  {coordinate, w bits, delta_left share bits,
+//                                  delta_right share bits}
+// eif_deep_gather_kernel makes both from the int4 records that
+// deep_level_order_kernel<int4> writes when it is handed each slot's
+// pre-order index as the "delta_left" word (and 0 as the leaf sentinel).
+//
+// Rows are staged as raw bits in their own element type (the widening at the
+// read is exact). PHT trees per barrier phase: the first S node records and
+// their S * nnz payload entries, copied linearly. A visit reads the record,
+// runs the dot over the payload (16 bytes a coordinate), compares, runs the
+// payload again for the taken shares and steps; a chain at a leaf reads no
+// payload and adds nothing. Phase A: lds_levels[t] trips from LDS, no flags;
+// phase B: records and payload from global memory, one wave vote a trip, the
+// first trip still from LDS below S.
+// ---------------------------------------------------------------------------
+
+__device__ __forceinline__ float widen_row(uint16_t b) {
+  return __uint_as_float((uint32_t)b << 16);  // bf16 -> f32
+}
+__device__ __forceinline__ float widen_row(f16_t b) {
+  union { uint16_t u; _Float16 h; } cv;
+  cv.u = (uint16_t)b;
+  return (float)cv.h;  // exact, subnormals included
+}
+__device__ __forceinline__ float widen_row(uint32_t b) {
+  return __uint_as_float(b);
+}
+
+// one thread per (tree, slot): the node record, and the payload of an
+// internal node gathered from its pre-order slot `old`
+__global__ void __launch_bounds__(DEEP_BT) eif_deep_gather_kernel(
+    const int4* __restrict__ lvl,      // [Tpad][M] {k | link << 12, offset,
+                                       //            old index, -}
+    const int32_t* __restrict__ hidx,  // [T][M0][nnz]
+    const int32_t* __restrict__ hw,    // [T][M0][nnz] f32 bits
+    const int32_t* __restrict__ dl,    // [T][M0][nnz] f32 bits
+    const int32_t* __restrict__ dr,    // [T][M0][nnz] f32 bits
+    int2* __restrict__ nodes,          // [Tpad][M]
+    int4* __restrict__ payload,        // [Tpad][M][nnz]
+    int32_t T, int32_t Tpad, int32_t M0, int32_t M, int32_t nnz, int32_t d) {
+  const int64_t total = (int64_t)Tpad * M;
+  for (int64_t g = (int64_t)blockIdx.x * DEEP_BT + threadIdx.x; g < total;
+       g += (int64_t)gridDim.x * DEEP_BT) {
+    const int t = (int)(g / M), i = (int)(g - (int64_t)t * M);
+    const int4 rec = lvl[g];
+    const bool internal = t < T && rec_link(rec.x) != i;
+    nodes[g] = make_int2(rec.x, internal ? rec.y : 0);
+    const int old = min(max(rec.z, 0), M0 - 1);
+    const int64_t src = ((int64_t)t * M0 + old) * nnz;
+    int4* dst = payload + g * nnz;
+    for (int j = 0; j < nnz; ++j)
+      dst[j] = internal ? make_int4(min(max(hidx[src + j], 0), d - 1),
+                                    hw[src + j], dl[src + j], dr[src + j])
+                        : make_int4(0, 0, 0, 0);
+  }
+}
+
+template <typename XT, int RPT, bool ACC_LDS>
+__global__ void __launch_bounds__(DEEP_BT) explain_extended_deep_kernel(
+    const XT* __restrict__ X,               // raw bf16/fp16/f32 bits
+    const int2* __restrict__ nodes,         // [Tpad][M]
+    const int4* __restrict__ payload,       // [Tpad][M][nnz]
+    const int32_t* __restrict__ lds_levels, // [Tpad]
+    float* __restrict__ out,                // [N][d] (pre-zeroed if !ACC_LDS)
+    int64_t N, int32_t d, int32_t nnz, int32_t Tpad, int32_t M, int32_t S,
+    int32_t PHT, int32_t height, float fT, int32_t finalize, int64_t rs,
+    int64_t cs) {
+  constexpr int FS = RPT * DEEP_BT;
+  constexpr uint32_t ALL = (1u << RPT) - 1u;
+  const int tid = threadIdx.x;
+  const int staged = min(S, M);  // records of a tree that the stage holds
+
+  int4* plds = (int4*)smem;                        // [PHT][S][nnz]
+  int2* tlds = (int2*)(plds + (size_t)PHT * S * nnz);  // [PHT][S]
+  float* acc = (float*)(tlds + PHT * S);           // [d][FS] when ACC_LDS
+  XT* rows = (XT*)(acc + (ACC_LDS ? d * FS : 0));  // [d][FS]
+
+  for (int64_t block_row0 = (int64_t)blockIdx.x * FS; block_row0 < N;
+       block_row0 += (int64_t)gridDim.x * FS) {
+    const int rows_here = (int)min((int64_t)FS, N - block_row0);
+
+    __syncthreads();  // previous tile's flush / readers done
+    stage_tile<XT, RPT, false>(rows, X, block_row0, rows_here, d, rs, cs);
+    if (ACC_LDS)
+      for (int i = tid; i < d * FS; i += DEEP_BT) acc[i] = 0.f;
+    // the first phase's barriers order these stores before the walk
+
+    const XT* rb[RPT];
+    float* ab[RPT];     // ACC_LDS: the row's column 0 in the tile
+    int64_t ooff[RPT];  // else: the row's offset in out
+    bool inb[RPT];
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+      const int j = tid + r * DEEP_BT;
+      rb[r] = rows + tile_slot<XT, RPT>(j);
+      ab[r] = acc + j;
+      ooff[r] = (block_row0 + j) * d;
+      inb[r] = j < rows_here;
+    }
+
+    for (int t = 0; t < Tpad; t += PHT) {
+      __syncthreads();  // previous phase's LDS readers done
+      for (int s = 0; s < PHT; ++s) {
+        const int2* nsrc = nodes + (int64_t)(t + s) * M;
+        const int4* psrc = payload + (int64_t)(t + s) * M * nnz;
+        int2* ndst = tlds + s * S;
+        int4* pdst = plds + (size_t)s * S * nnz;
+        for (int i = tid; i < staged; i += DEEP_BT) ndst[i] = nsrc[i];
+        for (int i = tid; i < staged * nnz; i += DEEP_BT) pdst[i] = psrc[i];
+      }
+      __syncthreads();
+
+#pragma unroll 1
+      for (int s = 0; s < PHT; ++s) {  // a row's trees: strictly in order
+        const int2* ts = tlds + s * S;
+        const int4* ps = plds + (size_t)s * S * nnz;
+        const int2* nb = nodes + (int64_t)(t + s) * M;
+        const int4* pb = payload + (int64_t)(t + s) * M * nnz;
+        const int la = min(lds_levels[t + s], height);
+        int cur[RPT];
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) cur[r] = 0;
+        // bit r of `live`: the chain has not read its leaf yet (phase B)
+        uint32_t live = ALL;
+
+        // One level of the thread's chains. MODE 0: phase A, every record
+        // and payload entry from LDS. MODE 1: the first tail trip, from LDS
+        // below S (the level after the staged ones straddles the stage's
+        // end, and a chain may rest at a staged leaf). MODE 2: from global.
+        auto trip = [&](auto mode) __attribute__((always_inline)) {
+          constexpr int MODE = decltype(mode)::value;
+          const uint32_t walk = MODE == 0 ? ALL : live;
+          int2 nd[RPT];
+          uint32_t in_lds = 0;
+#pragma unroll
+          for (int r = 0; r < RPT; ++r)
+            if (walk & (1u << r)) {
+              if (MODE == 0 || (MODE == 1 && cur[r] < S)) {
+                nd[r] = ts[cur[r]];
+                in_lds |= 1u << r;
+              } else {
+                nd[r] = nb[cur[r]];
+              }
+            }
+          // `on`: the chain reads an internal node on this trip
+          uint32_t on = 0;
+          int64_t pbase[RPT];
+#pragma unroll
+          for (int r = 0; r < RPT; ++r)
+            if (walk & (1u << r)) {
+              if (rec_link(nd[r].x) != cur[r]) on |= 1u << r;
+              else if (MODE != 0) live &= ~(1u << r);
+              pbase[r] = (int64_t)cur[r] * nnz;
+            }
+          auto entry = [&](int r, int j) __attribute__((always_inline)) {
+            return (in_lds & (1u << r)) ? ps[(int)pbase[r] + j]
+                                        : pb[pbase[r] + j];
+          };
+          float dot[RPT];
+#pragma unroll
+          for (int r = 0; r < RPT; ++r) dot[r] = 0.f;
+          for (int j = 0; j < nnz; ++j) {
+            int4 p[RPT];
+#pragma unroll
+            for (int r = 0; r < RPT; ++r)
+              if (on & (1u << r)) p[r] = entry(r, j);
+            XT xr[RPT];
+#pragma unroll
+            for (int r = 0; r < RPT; ++r)
+              if (on & (1u << r)) xr[r] = rb[r][p[r].x * FS];
+#pragma unroll
+            for (int r = 0; r < RPT; ++r)
+              if (on & (1u << r))
+                dot[r] = __fadd_rn(
+                    dot[r], __fmul_rn(__int_as_float(p[r].y), widen_row(xr[r])));
+          }
+          uint32_t left = 0;
+#pragma unroll
+          for (int r = 0; r < RPT; ++r)
+            if ((on & (1u << r)) && dot[r] < __int_as_float(nd[r].y))
+              left |= 1u << r;
+          // the taken edge's shares, ascending j over the node's k
+          // coordinates; per row: read, add, write before the next j
+          for (int j = 0; j < nnz; ++j) {
+            uint32_t add = 0;
+            int4 p[RPT];
+#pragma unroll
+            for (int r = 0; r < RPT; ++r)
+              if ((on & (1u << r)) && j < rec_feat(nd[r].x)) {
+                p[r] = entry(r, j);
+                add |= 1u << r;
+              }
+            float a[RPT];
+            if (ACC_LDS) {
+#pragma unroll
+              for (int r = 0; r < RPT; ++r)
+                if (add & (1u << r)) a[r] = ab[r][p[r].x * FS];
+            } else {
+#pragma unroll
+              for (int r = 0; r < RPT; ++r) {
+                if ((add & (1u << r)) &&
+                    (!inb[r] || (uint32_t)p[r].x >= (uint32_t)d))
+                  add &= ~(1u << r);
+                if (add & (1u << r)) a[r] = out[ooff[r] + p[r].x];
+              }
+            }
+#pragma unroll
+            for (int r = 0; r < RPT; ++r)
+              if (add & (1u << r)) {
+                const float v = __fadd_rn(
+                    a[r], __int_as_float((left & (1u << r)) ? p[r].z : p[r].w));
+                if (ACC_LDS) ab[r][p[r].x * FS] = v;
+                else out[ooff[r] + p[r].x] = v;
+              }
+          }
+#pragma unroll
+          for (int r = 0; r < RPT; ++r)
+            if (on & (1u << r))
+              cur[r] = rec_link(nd[r].x) - (int)((left >> r) & 1u);
+        };
+
+        for (int it = 0; it < la; ++it)
+          trip(std::integral_constant<int, 0>{});
+        trip(std::integral_constant<int, 1>{});
+        // a chain at depth `height` is a leaf: height - la more trips read it
+        for (int k = la; k < height && __any(live != 0); ++k)
+          trip(std::integral_constant<int, 2>{});
+      }
+    }
+
+    if (ACC_LDS) {
+      __syncthreads();  // every row's accumulators final
+      const int total = rows_here * d;
+      float* o = out + block_row0 * d;
+      for (int g = tid; g < total; g += DEEP_BT) {
+        const int r = (int)((uint32_t)g / (uint32_t)d), c = g - r * d;
+        const float v = acc[c * FS + r];
+        o[g] = finalize ? div32_exact(v, fT) : v;
+      }
+    } else if (finalize) {
+#pragma unroll
+      for (int r = 0; r < RPT; ++r)
+        if (inb[r])
+          for (int c = 0; c < d; ++c) {
+            float* o = out + ooff[r] + c;
+            *o = div32_exact(*o, fT);
+          }
+    }
+  }
+}
+
 }  // namespace deep
 
 // host-side launchers (bindings.cpp is compiled by g++)
@@ -752,6 +1020,61 @@ hipError_t launch_explain_forest_deep(RowDtype dt, int rpt, bool acc_lds,
   else LXD(uint32_t);
 #undef LXD
 #undef LXD1
+  return hipGetLastError();
+}
+
+// lvl: the int4 records of launch_explain_deep_level_order run with every
+// slot's pre-order index as its delta_left word and d = 0
+void launch_eif_deep_gather(const void* lvl, const int32_t* hidx,
+                            const int32_t* hw, const int32_t* dl,
+                            const int32_t* dr, void* nodes, void* payload,
+                            int32_t T, int32_t Tpad, int32_t M0, int32_t M,
+                            int32_t nnz, int32_t d, hipStream_t stream) {
+  const int64_t total = (int64_t)Tpad * M;
+  const int blocks =
+      (int)std::min<int64_t>((total + DEEP_BT - 1) / DEEP_BT, 65535);
+  hipLaunchKernelGGL(deep::eif_deep_gather_kernel, dim3(blocks), dim3(DEEP_BT),
+                     0, stream, (const int4*)lvl, hidx, hw, dl, dr,
+                     (int2*)nodes, (int4*)payload, T, Tpad, M0, M, nnz, d);
+}
+
+hipError_t launch_explain_extended_deep(
+    RowDtype dt, int rpt, bool acc_lds, const void* X, const void* nodes,
+    const void* payload, const int32_t* lds_levels, float* out, int64_t N,
+    int32_t d, int32_t nnz, int64_t rs, int64_t cs, int32_t Tpad, int32_t M,
+    int32_t S, int32_t trees_per_phase, int32_t height, float fT, int finalize,
+    size_t lds, int blocks, hipStream_t stream) {
+  // the binding's two shapes, as in launch_explain_forest_deep
+  if ((rpt != 2 || !acc_lds) && (rpt != 1 || acc_lds))
+    return hipErrorInvalidValue;
+  if (trees_per_phase < 1 || Tpad % trees_per_phase != 0)
+    return hipErrorInvalidValue;
+  hipError_t err = hipSuccess;
+#define LXE1(XT, RPT, AL)                                                     \
+  do {                                                                        \
+    const void* fn =                                                          \
+        (const void*)deep::explain_extended_deep_kernel<XT, RPT, AL>;         \
+    if (lds > 64 * 1024)                                                      \
+      err = hipFuncSetAttribute(                                              \
+          fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
+    if (err != hipSuccess) return err;                                        \
+    hipLaunchKernelGGL((deep::explain_extended_deep_kernel<XT, RPT, AL>),     \
+                       dim3(blocks), dim3(DEEP_BT), lds, stream,              \
+                       (const XT*)X, (const int2*)nodes,                      \
+                       (const int4*)payload, lds_levels, out, N, d, nnz,      \
+                       Tpad, M, S, trees_per_phase, height, fT, finalize, rs, \
+                       cs);                                                   \
+  } while (0)
+#define LXE(XT)                                                               \
+  do {                                                                        \
+    if (acc_lds) LXE1(XT, 2, true);                                           \
+    else LXE1(XT, 1, false);                                                  \
+  } while (0)
+  if (dt == ROW_BF16) LXE(uint16_t);
+  else if (dt == ROW_F16) LXE(deep::f16_t);
+  else LXE(uint32_t);
+#undef LXE
+#undef LXE1
   return hipGetLastError();
 }
 

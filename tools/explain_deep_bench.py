@@ -9,6 +9,10 @@ the output, IFA_EXPLAIN_FORCE_GLOBAL_ACC=1), and with IFA_EXPLAIN_DEEP=0
 Usage: python tools/explain_deep_bench.py [--rows 5000000] [--features 32]
        [--max-samples 65536] [--trees 100] [--dtype bf16] [--repeats 5]
        [--calls 3] [--cpu-rows 20000] [--stages 2] [--out FILE]
+       [--extended [--extension-level L]]
+
+--extended fits an ExtendedIsolationForest instead and times the deep EIF
+route (explain_extended_deep) the same way.
 
 Fits one IsolationForest on a resident [N, d] CUDA matrix (contamination 0),
 explains once per variant to make and cache the packs and tables (timed as
@@ -48,6 +52,10 @@ def main():
                     help="forced stages to time beside the default, a,b,...; "
                          "a trailing g (1024g, or g alone for the default "
                          "stage) adds IFA_EXPLAIN_FORCE_GLOBAL_ACC=1")
+    ap.add_argument("--extended", action="store_true",
+                    help="an ExtendedIsolationForest (explain_extended_deep)")
+    ap.add_argument("--extension-level", type=int, default=None,
+                    help="with --extended; default: fully extended")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     for st in filter(None, args.stages.split(",")):
@@ -59,7 +67,7 @@ def main():
         VARIANTS[f"deep_stage{st}"] = env
     VARIANTS["cpu"] = {"IFA_EXPLAIN_DEEP": "0"}
 
-    from isolation_forest_amd import IsolationForest
+    from isolation_forest_amd import ExtendedIsolationForest, IsolationForest
     from isolation_forest_amd.ops import gpu_engine, load_extension
 
     load_extension()
@@ -73,9 +81,12 @@ def main():
     torch.cuda.synchronize()
 
     t0 = time.perf_counter()
-    model = IsolationForest(numEstimators=args.trees,
-                            maxSamples=float(args.max_samples),
-                            randomSeed=3).fit(X)
+    kw = dict(numEstimators=args.trees, maxSamples=float(args.max_samples),
+              randomSeed=3)
+    if args.extended and args.extension_level is not None:
+        kw["extensionLevel"] = args.extension_level
+    model = (ExtendedIsolationForest if args.extended
+             else IsolationForest)(**kw).fit(X)
     torch.cuda.synchronize()
     t_fit = time.perf_counter() - t0
     forest = model.forest
@@ -123,10 +134,15 @@ def main():
                 "spread_ms_per_million_rows": round(
                     (max(v) - min(v)) * 1e9 / rows, 2)}
 
-    rec_bytes = {"/".join(map(str, key[2])): aos.numel() * aos.element_size()
-                 for key, (aos, _, _) in model._gpu_forest_cache.items()}
+    rec_bytes = {
+        "/".join(map(str, key[2])): sum(
+            a.numel() * a.element_size()
+            for a in (aos, extra.get("payload")) if a is not None)
+        for key, (aos, _, extra) in model._gpu_forest_cache.items()}
     out = {
         "tool": "explain_deep_bench", "rows": args.rows,
+        "extended": args.extended,
+        "hyperplane_width": int(getattr(forest, "nnz", 1)),
         "features": args.features, "max_samples": int(forest.num_samples),
         "trees": int(forest.num_trees), "dtype": args.dtype,
         "calls_per_window": args.calls, "fit_s": round(t_fit, 2),
