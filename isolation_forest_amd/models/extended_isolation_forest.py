@@ -129,6 +129,13 @@ class ExtendedIsolationForestModel(ModelBase):
         if isinstance(X, torch.Tensor) and X.is_cuda:
             from ..ops import gpu_engine
 
+            # large bags: the deep LDS/L2 walk where it has a route, as
+            # _build_local picks build_extended_forest_large
+            if (self.forest.feature.shape[1] > 32767
+                    and X.dtype in gpu_engine._ROW_KINDS
+                    and gpu_engine.large_score_route(
+                        self.forest, int(X.shape[1]), X.dtype) == "deep"):
+                return gpu_engine.score_extended_forest_deep(self, X)
             return gpu_engine.score_extended_forest(self, X)
         Xc = X.contiguous().float().numpy() if isinstance(X, torch.Tensor) else X
         return torch.from_numpy(cpu_engine.score_extended_forest(self.forest, Xc))

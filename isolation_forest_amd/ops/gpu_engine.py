@@ -843,6 +843,33 @@ def _nodes_explain_eif_deep_host(forest):
             max(max_depth, 1))
 
 
+def _nodes_eif_deep_host(forest):
+    """Host half of the eif deep pack (ops/hip/deep_kernels.hip): the
+    pre-order arrays of an extended forest TRIMMED to the largest
+    node_count, with no [T, 2^(H+1) - 1, ...] temporary. int32 [T, M0]: the
+    coordinate count k of an internal node (-1 for leaves and dead slots),
+    the pre-order right child, and one value word a node: the f32 bits of
+    the offset, or for a leaf of f32(depth) + f32(value), what
+    cpu_engine.path_lengths_extended adds per tree; int32 [T, M0, nnz]: the
+    coordinates and the f32 bits of the weights. Returns (feat, right, vw,
+    node_count, hidx, hw, max_depth)."""
+    nc = np.ascontiguousarray(forest.node_count, dtype=np.int32)
+    m0 = max(int(nc.max(initial=1)), 1)
+    feat = np.ascontiguousarray(forest.feature[:, :m0])
+    right = np.ascontiguousarray(forest.right[:, :m0], dtype=np.int32)
+    internal = feat >= 0
+    leaf = feat == ExtendedForest.LEAF
+    depth = _node_depths(feat, right)
+    value = np.ascontiguousarray(forest.value[:, :m0], dtype=np.float32)
+    vw = np.where(leaf, depth.astype(np.float32) + value, value)
+    live = internal | leaf
+    max_depth = int(depth[live].max()) if live.any() else 0
+    bits = lambda a: np.ascontiguousarray(a, dtype=np.float32).view(np.int32)  # noqa: E731
+    return (np.where(internal, feat, -1).astype(np.int32), right, bits(vw),
+            nc, np.ascontiguousarray(forest.hyper_idx[:, :m0], dtype=np.int32),
+            bits(forest.hyper_w[:, :m0]), max(max_depth, 1))
+
+
 def _nodes_packed_explain(forest, d_sentinel: int, bf16):
     """16-byte node records for explain_forest_kernel (`bf16` is the row
     kind, as in _nodes_packed_v4):
@@ -1388,10 +1415,10 @@ def _device_forest(model, device, v4_key=None):
     on the row KIND, not on "is it 16-bit": bf16 and fp16 keys differ, and
     u32 records under a u16 kernel score silently wrong. The "shap" entry
     is (table words, per-tree word offsets, {host offsets, weights}).
-    ("explain_eif_deep", stage) holds f32 offsets and weights and serves
-    every row kind."""
+    ("explain_eif_deep", stage) and ("eif_deep", stage) hold f32 offsets and
+    weights and serve every row kind."""
     if isinstance(v4_key, tuple) and v4_key[0] not in (
-            "eif_dense", "eif_dense3", "explain_eif_deep"):
+            "eif_dense", "eif_dense3", "explain_eif_deep", "eif_deep"):
         v4_key = v4_key[:-1] + (_row_kind(v4_key[-1]),)
     key = (str(device), id(model.forest), v4_key)
     cache = model._gpu_forest_cache
@@ -1555,6 +1582,18 @@ def _device_forest(model, device, v4_key=None):
                     *(torch.from_numpy(a).to(device) for a in arrays),
                     max(_coord_range(forest)[1], 0) + 1, v4_key[1])
             extra["height"] = max_depth
+        elif isinstance(v4_key, tuple) and v4_key[0] == "eif_deep":
+            # ("eif_deep", stage): aos = the level-order node records,
+            # ncount = lds_levels, extra["hyper"] = the {coordinate, w}
+            # entries, all made on the device
+            from . import load_extension as _packing_extension
+
+            *arrays, max_depth = _nodes_eif_deep_host(forest)
+            aos, extra["hyper"], ncount = \
+                _packing_extension().eif_deep_pack(
+                    *(torch.from_numpy(a).to(device) for a in arrays),
+                    max(_coord_range(forest)[1], 0) + 1, v4_key[1])
+            extra["height"] = max_depth
         elif v4_key == "eif_wide":
             packed = _eif_packed_wide(forest)
             aos = torch.from_numpy(packed).to(device)
@@ -1642,15 +1681,35 @@ def _deep_stage(kind: str, d: int) -> int:
     return int(_packing_extension().deep_stage(kind, int(d)))
 
 
+def _eif_deep_stage(kind: str, d: int, nnz: int) -> int:
+    """Node records per tree the deep EIF scoring walk stages for these rows
+    and this hyperplane width now (0: the row tile leaves no room); see
+    _deep_stage."""
+    from . import load_extension as _packing_extension
+
+    return int(_packing_extension().eif_deep_stage(kind, int(d), int(nnz)))
+
+
 def large_score_route(forest, d: int, dtype) -> str:
-    """The kernel family ``score_forest`` runs for a standard forest past the
-    packed 15-bit node ids: ``"deep"`` (compact level-order records, top
-    levels in LDS, tail from L2) or ``"wide"`` (int4 records, one global read
-    per visit). ``IFA_SCORE_DEEP=0`` keeps the wide route; so do forests past
+    """The kernel family that scores a forest past the packed 15-bit node
+    ids: ``"deep"`` (compact level-order records, top levels in LDS, tail
+    from L2) or ``"wide"`` (int4 records, one global read per visit; for an
+    extended forest the entries of the hyperplane too).
+    ``IFA_SCORE_DEEP=0`` keeps the wide route; so do forests past
     ``DEEP_MAX_NODES`` nodes a tree or 4094 features, and rows too wide for
-    the key tile to leave a stage in LDS."""
+    the tile to leave a stage in LDS. An extended forest also stays wide
+    with a hyperplane coordinate outside ``[0, min(d - 1, 4094)]`` or more
+    than 4094 coordinates a hyperplane."""
     if os.environ.get("IFA_SCORE_DEEP", "1") == "0":
         return "wide"
+    if isinstance(forest, ExtendedForest):
+        if int(np.max(forest.node_count, initial=1)) > DEEP_MAX_NODES:
+            return "wide"
+        cmin, cmax = _coord_range(forest)
+        if cmin < 0 or cmax > min(d - 1, 4094) or max(d, forest.nnz) > 4094:
+            return "wide"
+        stage = _eif_deep_stage(_row_kind(dtype), d, forest.nnz)
+        return "deep" if stage > 0 else "wide"
     if not _deep_fits(forest, d):
         return "wide"
     return "deep" if _deep_stage(_row_kind(dtype), d) > 0 else "wide"
@@ -1699,7 +1758,35 @@ def _eif_uniform_nnz(forest) -> bool:
     return u
 
 
+def score_extended_forest_deep(model, X: torch.Tensor,
+                               finalize: bool = True) -> torch.Tensor:
+    """Scores an extended forest whose node arrays are wider than 32767 on
+    the deep route (score_extended_deep_kernel), where ``large_score_route``
+    says ``"deep"``; anything else is an error, not a fall-back. Bitwise
+    equal to cpu_engine.score_extended_forest, like the wide kernel."""
+    forest = model.forest
+    d = int(X.shape[1])
+    kind = _row_kind(X.dtype)
+    if large_score_route(forest, d, kind) != "deep":
+        raise ValueError(
+            f"large_score_route keeps {kind} rows of {d} columns on the wide "
+            "kernel for this forest; score it with score_extended_forest")
+    stage = _eif_deep_stage(kind, d, forest.nnz)
+    nodes, lds_levels, extra = _device_forest(
+        model, X.device, v4_key=("eif_deep", stage))
+    return load_extension().score_extended_deep(
+        _rows_in_place(X), nodes, extra["hyper"], lds_levels,
+        forest.num_trees, extra["height"], stage,
+        float(avg_path_length(forest.num_samples)), finalize, forest.nnz)
+
+
 def score_extended_forest(model, X: torch.Tensor, finalize: bool = True) -> torch.Tensor:
+    """Scores an extended forest on the packed routes, and past their caps
+    (node arrays wider than 32767, more than 4094 coordinates) on the wide
+    kernel, always. The deep route for large bags is a separate entry point,
+    score_extended_forest_deep, which ExtendedIsolationForestModel.score
+    picks with large_score_route, as the model picks
+    build_extended_forest_large for the build."""
     ext = load_extension()
     forest = model.forest
     c = float(avg_path_length(forest.num_samples))

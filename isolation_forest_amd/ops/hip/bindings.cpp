@@ -229,6 +229,18 @@ hipError_t launch_explain_extended_deep(
     int32_t d, int32_t nnz, int64_t rs, int64_t cs, int32_t Tpad, int32_t M,
     int32_t S, int32_t trees_per_phase, int32_t height, float fT, int finalize,
     size_t lds, int blocks, hipStream_t stream);
+int32_t eif_deep_hyper_stride(int32_t nnz);
+void launch_eif_score_gather(const void* lvl, const int32_t* vw,
+                             const int32_t* hidx, const int32_t* hw,
+                             void* nodes, void* hyper, int32_t T, int32_t Tpad,
+                             int32_t M0, int32_t M, int32_t nnz, int32_t d,
+                             hipStream_t stream);
+hipError_t launch_score_extended_deep(
+    RowDtype dt, int rpt, int phase, const void* X, const void* nodes,
+    const void* hyper, const int32_t* lds_levels, float* out, int64_t N,
+    int32_t d, int32_t nnz, int64_t rs, int64_t cs, int32_t Tpad, int32_t M,
+    int32_t S, int32_t height, float fT, float c_norm, int finalize,
+    size_t lds, int blocks, hipStream_t stream);
 
 // bag_kernels.hip
 int launch_bag_sample_lds(int64_t* out, int32_t* err, uint64_t seed,
@@ -1797,6 +1809,218 @@ torch::Tensor explain_extended_deep(torch::Tensor X, torch::Tensor nodes,
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// scoring for the same forests (score_extended_deep_kernel): 8-byte node
+// records and an 8-byte {coordinate, w} entry per hyperplane coordinate
+// ---------------------------------------------------------------------------
+
+constexpr int kSEDeepStage = 512;    // a larger stage comes before more trees
+                                     // a phase up to here,
+constexpr int kSEDeepMaxStage = 1024;  // after them up to here
+constexpr int kSEDeepMinStage = 16;  // least, while another shape is a choice
+
+struct ScoreEifDeepCfg {
+  int rpt, phase, stage;  // stage 0: the row tile leaves no room for a stage
+  size_t lds;
+};
+
+// Rows per thread, trees per barrier phase and the stage S from the LDS left
+// beside the row tile. A staged node costs 8 + 8 * HS bytes (HS: nnz rounded
+// up to even). The shapes in order: two blocks resident per CU before one,
+// two rows a thread before one; within a shape the largest power of two S
+// from kSEDeepStage down to kSEDeepMinStage that fits with one tree a phase,
+// then as many trees a phase (4, 2, 1) as fit beside it, then S doubled up
+// to kSEDeepMaxStage while that still fits. A larger stage beat more trees a
+// phase by 33 % where only 32 to 128 nodes fit (nnz = d = 32) and by 2 %
+// between 512 and 1024 (nnz = 2): profiles/score_eif_deep.md. The last shape
+// goes down to S = 2.
+// IFA_EIF_DEEP_STAGE=<records> forces S to any power of two >= 2 and
+// IFA_EIF_DEEP_PHASE=4|2|1 the trees per phase; a forced pair that no shape
+// fits leaves no route.
+ScoreEifDeepCfg pick_score_eif_deep_cfg(int elem_bytes, int64_t d,
+                                        int64_t nnz) {
+  int forced_s = 0, forced_ph = 0;
+  if (const char* e = getenv("IFA_EIF_DEEP_STAGE")) {
+    const long v = atol(e);
+    if (v >= 2 && v <= kDeepMaxNodes && (v & (v - 1)) == 0) forced_s = (int)v;
+  }
+  if (const char* e = getenv("IFA_EIF_DEEP_PHASE")) {
+    const long v = atol(e);
+    if (v == 4 || v == 2 || v == 1) forced_ph = (int)v;
+  }
+  const size_t node = 8 + 8 * (size_t)ifa::eif_deep_hyper_stride((int32_t)nnz);
+  struct Shape {
+    size_t budget;
+    int rpt, s_lo;
+  };
+  const size_t one_block = (size_t)150 * 1024;
+  const Shape shapes[] = {{kMaxLds / 2, 2, kSEDeepMinStage},
+                          {kMaxLds / 2, 1, kSEDeepMinStage},
+                          {one_block, 2, kSEDeepMinStage},
+                          {one_block, 1, 2}};
+  for (const Shape& sh : shapes) {
+    const size_t tile = (size_t)sh.rpt * 256 * (size_t)d * (size_t)elem_bytes;
+    for (int s = forced_s ? forced_s : kSEDeepStage;
+         s >= (forced_s ? forced_s : sh.s_lo); s >>= 1)
+      for (int ph : {4, 2, 1}) {
+        if (forced_ph && ph != forced_ph) continue;
+        if (tile + (size_t)ph * s * node > sh.budget) continue;
+        while (!forced_s && 2 * s <= kSEDeepMaxStage &&
+               tile + (size_t)ph * 2 * s * node <= sh.budget)
+          s *= 2;
+        return {sh.rpt, ph, s, tile + (size_t)ph * s * node};
+      }
+  }
+  return {0, 0, 0, 0};
+}
+
+// the stage score_extended_deep runs rows of this kind and width with now
+// for hyperplanes of nnz coordinates, or 0 where it has no route for them
+int64_t eif_deep_stage(const std::string& dtype, int64_t d, int64_t nnz) {
+  if (d < 1 || d > 4094 || nnz < 1 || nnz > 4094) return 0;
+  return pick_score_eif_deep_cfg(elem_bytes_of(dtype), d, nnz).stage;
+}
+
+// (rows per thread, trees per barrier phase, stage) of the instantiation
+// these shapes run, or (0, 0, 0) where eif_deep_stage is 0
+std::tuple<int64_t, int64_t, int64_t> score_eif_deep_cfg(
+    const std::string& dtype, int64_t d, int64_t nnz) {
+  if (d < 1 || d > 4094 || nnz < 1 || nnz > 4094) return {0, 0, 0};
+  const ScoreEifDeepCfg cfg =
+      pick_score_eif_deep_cfg(elem_bytes_of(dtype), d, nnz);
+  return {cfg.rpt, cfg.phase, cfg.stage};
+}
+
+// Trimmed pre-order arrays of an extended forest -> the eif deep pack for a
+// stage of `stage`: node records int32 [Tpad, M, 2], entries int32
+// [Tpad, M, HS, 2] and lds_levels int32 [Tpad]. feat [T, M0] is the
+// coordinate count k of an internal node (< 0: leaf), vw the f32 bits of its
+// offset or of a leaf's depth + value; hidx and hw [T, M0, nnz] are the
+// coordinates and the f32 bits of the weights. The level order is
+// deep_level_order_kernel<int2>'s, run with every slot's own pre-order index
+// in place of the threshold; the gather then writes the value words and
+// moves each node's entries to its new slot. Coordinates are clamped to
+// [0, coord_cap).
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> eif_deep_pack(
+    torch::Tensor feat, torch::Tensor right, torch::Tensor vw,
+    torch::Tensor ncount, torch::Tensor hidx, torch::Tensor hw,
+    int64_t coord_cap, int64_t stage) {
+  for (const torch::Tensor* a : {&feat, &right, &vw}) {
+    CHECK_CUDA(*a);
+    CHECK_CONTIG(*a);
+    TORCH_CHECK(a->dim() == 2 && a->scalar_type() == torch::kInt32 &&
+                    a->sizes() == feat.sizes(),
+                "feat, right and vw must be int32 [T, M0]");
+  }
+  const int64_t T = feat.size(0), M0 = feat.size(1);
+  for (const torch::Tensor* a : {&hidx, &hw}) {
+    CHECK_CUDA(*a);
+    CHECK_CONTIG(*a);
+    TORCH_CHECK(a->dim() == 3 && a->scalar_type() == torch::kInt32 &&
+                    a->sizes() == hidx.sizes() && a->size(0) == T &&
+                    a->size(1) == M0,
+                "hidx and hw must be int32 [T, M0, nnz]");
+  }
+  CHECK_CUDA(ncount);
+  CHECK_CONTIG(ncount);
+  TORCH_CHECK(ncount.scalar_type() == torch::kInt32 && ncount.dim() == 1 &&
+                  ncount.size(0) == T,
+              "ncount must be int32 [T]");
+  const int64_t nnz = hidx.size(2);
+  TORCH_CHECK(M0 >= 1 && M0 <= kDeepMaxNodes, "deep links are 20 bits");
+  TORCH_CHECK(nnz >= 1 && nnz <= 4094 && coord_cap >= 1 && coord_cap <= 4094,
+              "hyperplane widths and coordinates are 12 bits");
+  TORCH_CHECK(stage >= 2 && stage <= kDeepMaxNodes &&
+                  (stage & (stage - 1)) == 0,
+              "stage must be a power of two >= 2");
+  TORCH_CHECK(T <= 65535 * kDeepPhase, "too many trees");
+  const int64_t Tpad = (T + kDeepPhase - 1) / kDeepPhase * kDeepPhase;
+  const int64_t M = M0;
+  const int64_t hs = ifa::eif_deep_hyper_stride((int32_t)nnz);
+  auto nodes = torch::empty({Tpad, M, 2}, feat.options());
+  auto hyper = torch::empty({Tpad, M, hs, 2}, feat.options());
+  auto levels = torch::empty({Tpad}, feat.options());
+  if (T == 0) return {nodes, hyper, levels};
+  auto lvl = torch::empty({Tpad, M, 2}, feat.options());
+  auto old = torch::arange(M0, feat.options()).expand({T, M0}).contiguous();
+  auto front = torch::empty({2, T, M0}, feat.options());
+  int32_t* fr = front.data_ptr<int32_t>();
+  // leaf sentinel 0: a leaf record is k = 0 with a link to itself
+  ifa::launch_deep_level_order(
+      feat.data_ptr<int32_t>(), right.data_ptr<int32_t>(),
+      old.data_ptr<int32_t>(), ncount.data_ptr<int32_t>(), (uint32_t*)fr,
+      (uint32_t*)(fr + T * M0), lvl.data_ptr<int32_t>(),
+      levels.data_ptr<int32_t>(), (int32_t)T, (int32_t)Tpad, (int32_t)M0,
+      (int32_t)M, (int32_t)stage, 0, current_stream());
+  ifa::launch_eif_score_gather(
+      lvl.data_ptr<int32_t>(), vw.data_ptr<int32_t>(),
+      hidx.data_ptr<int32_t>(), hw.data_ptr<int32_t>(),
+      nodes.data_ptr<int32_t>(), hyper.data_ptr<int32_t>(), (int32_t)T,
+      (int32_t)Tpad, (int32_t)M0, (int32_t)M, (int32_t)nnz,
+      (int32_t)coord_cap, current_stream());
+  return {nodes, hyper, levels};
+}
+
+// Returns the f32 [N] scores (path sums when !finalize). `stage` is the one
+// the pack's lds_levels were counted for; nnz is the forest's hyperplane
+// width where the pack's entry stride (nnz rounded up to even) does not say
+// it: 0 means the stride itself.
+torch::Tensor score_extended_deep(torch::Tensor X, torch::Tensor nodes,
+                                  torch::Tensor hyper,
+                                  torch::Tensor lds_levels, int64_t num_trees,
+                                  int64_t height, int64_t stage, double c_norm,
+                                  bool finalize, int64_t nnz) {
+  CHECK_CUDA(X);
+  for (const torch::Tensor* a : {&nodes, &hyper, &lds_levels}) {
+    CHECK_CUDA(*a);
+    CHECK_CONTIG(*a);
+    TORCH_CHECK(a->scalar_type() == torch::kInt32, "the pack is int32");
+  }
+  check_x(X);
+  const XLayout xl = check_x_layout(X);
+  TORCH_CHECK(nodes.dim() == 3 && nodes.size(2) == 2,
+              "nodes must be int32 [Tpad, M, 2]");
+  const int64_t N = X.size(0), d = X.size(1);
+  const int64_t Tpad = nodes.size(0), M = nodes.size(1);
+  TORCH_CHECK(hyper.dim() == 4, "hyper must be int32 [Tpad, M, HS, 2]");
+  if (nnz == 0) nnz = hyper.size(2);
+  TORCH_CHECK(d >= 1 && d <= 4094 && nnz >= 1 && nnz <= 4094,
+              "scoring supports 1 <= d, nnz <= 4094 (12-bit fields)");
+  TORCH_CHECK(hyper.size(0) == Tpad &&
+                  hyper.size(1) == M &&
+                  hyper.size(2) == ifa::eif_deep_hyper_stride((int32_t)nnz) &&
+                  hyper.size(3) == 2,
+              "hyper must be int32 [Tpad, M, nnz rounded up to even, 2]");
+  TORCH_CHECK(Tpad % kDeepPhase == 0 && num_trees >= 1 && num_trees <= Tpad,
+              "deep tree count must be padded to the phase");
+  TORCH_CHECK(M >= 1 && M <= kDeepMaxNodes,
+              "deep records hold at most 2^20 nodes a tree");
+  TORCH_CHECK(lds_levels.dim() == 1 && lds_levels.size(0) == Tpad,
+              "lds_levels must be int32 [Tpad]");
+  TORCH_CHECK(height >= 1 && height <= 64, "height out of range");
+  const ifa::RowDtype dt = row_dtype(X);
+  const ScoreEifDeepCfg cfg =
+      pick_score_eif_deep_cfg(ifa::row_elem_bytes(dt), d, nnz);
+  TORCH_CHECK(cfg.stage > 0 && cfg.stage == stage,
+              "the pack was staged for ", stage, " records a tree, rows of "
+              "this kind and width run ", cfg.stage);
+  auto out = torch::empty({N}, X.options().dtype(torch::kFloat32));
+  if (N == 0) return out;
+  const int64_t rows_per_block = (int64_t)cfg.rpt * 256;
+  const int blocks = (int)std::min<int64_t>(
+      (N + rows_per_block - 1) / rows_per_block, 8192);
+  const hipError_t err = ifa::launch_score_extended_deep(
+      dt, cfg.rpt, cfg.phase, X.data_ptr(), nodes.data_ptr<int32_t>(),
+      hyper.data_ptr<int32_t>(), lds_levels.data_ptr<int32_t>(),
+      out.data_ptr<float>(), N, (int32_t)d, (int32_t)nnz, xl.rs, xl.cs,
+      (int32_t)Tpad, (int32_t)M, (int32_t)cfg.stage, (int32_t)height,
+      (float)num_trees, (float)c_norm, finalize ? 1 : 0, cfg.lds, blocks,
+      current_stream());
+  TORCH_CHECK(err == hipSuccess, "score_extended_deep launch failed (",
+              cfg.lds, " B of LDS): ", hipGetErrorString(err));
+  return out;
+}
+
 torch::Tensor score_extended_wide(torch::Tensor X, torch::Tensor nodes_wide,
                                   torch::Tensor hidx, torch::Tensor hw,
                                   double c_norm, bool finalize) {
@@ -2165,5 +2389,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-coordinate payload, lds_levels");
   m.def("explain_extended_deep", &explain_extended_deep,
         "EIF attribution past 15-bit node ids: LDS top levels, L2 tail");
+  m.def("eif_deep_stage", &eif_deep_stage,
+        "records per tree score_extended_deep stages for (dtype, d, nnz); "
+        "0: none");
+  m.def("score_eif_deep_cfg", &score_eif_deep_cfg,
+        "(rows per thread, trees per phase, stage) score_extended_deep runs "
+        "for (dtype, d, nnz)");
+  m.def("eif_deep_pack", &eif_deep_pack,
+        "trimmed pre-order extended forest -> level-order node records, "
+        "{coordinate, w} entries, lds_levels");
+  m.def("score_extended_deep", &score_extended_deep,
+        "EIF scoring past 15-bit node ids: LDS top levels, L2 tail",
+        py::arg("X"), py::arg("nodes"), py::arg("hyper"),
+        py::arg("lds_levels"), py::arg("num_trees"), py::arg("height"),
+        py::arg("stage"), py::arg("c"), py::arg("finalize"),
+        py::arg("nnz") = 0);
   m.attr("WAVE") = 64;
 }

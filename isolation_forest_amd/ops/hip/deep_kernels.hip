@@ -923,6 +923,302 @@ __global__ void __launch_bounds__(DEEP_BT) explain_extended_deep_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// extended scoring (docs/DESIGN.md §3b): the two-phase walk over hyperplane
+// nodes with nothing to add along the path. BITWISE equal to
+// cpu_engine.path_lengths_extended: per visit the dot is
+// fadd(dot, fmul(w_j, x_j)) from 0.f in ascending j over all nnz stored
+// coordinates (no FMA), the step is cur = link - (dot < offset) (NaN goes
+// right), and a row's leaf values f32(depth) + f32(value) are added in tree
+// order. Only that last add is ordered, so a thread walks the PH trees of a
+// phase together: RPT * PH independent chains.
+//
+// Pack ("eif deep"), level order as above, f32 throughout (every row kind):
+//   nodes  int2 [Tpad][M]      x = k | link << 12, y = f32 bits of the offset;
+//                              a leaf has link = its own index, k = 0 and
+//                              y = f32 bits of depth + value
+//   hyper  int2 [Tpad][M][HS]  {coordinate, f32 bits of w}; HS = nnz rounded
+//                              up to even (1 stays 1), so that the entries of
+//                              a node start on 16 bytes and two are read per
+//                              128-bit load. Leaves and the pad entry are zero;
+//                              the pad entry is never read.
+// eif_score_gather_kernel makes both from the int2 records that
+// deep_level_order_kernel<int2> writes when it is handed each slot's
+// pre-order index as its threshold word (and 0 as the leaf sentinel).
+//
+// A chain is at a leaf when the record's link is its own index; the step is
+// predicated on that, never on the dot: a leaf's entries are {0, 0.f} and
+// 0 * inf is NaN. Phase A reads a resting chain's record and entries again
+// (all inside the stage); phase B loads nothing for a finished chain and
+// nothing past the first entry load for a chain that turns out to be at its
+// leaf.
+// ---------------------------------------------------------------------------
+
+__host__ __device__ __forceinline__ int eif_hyper_stride(int nnz) {
+  return nnz == 1 ? 1 : (nnz + 1) & ~1;
+}
+
+// one thread per (tree, slot): the node record with the host's value word,
+// and the entries of an internal node gathered from its pre-order slot
+__global__ void __launch_bounds__(DEEP_BT) eif_score_gather_kernel(
+    const int2* __restrict__ lvl,      // [Tpad][M] {k | link << 12, old index}
+    const int32_t* __restrict__ vw,    // [T][M0] offset / leaf value bits
+    const int32_t* __restrict__ hidx,  // [T][M0][nnz]
+    const int32_t* __restrict__ hw,    // [T][M0][nnz] f32 bits
+    int2* __restrict__ nodes,          // [Tpad][M]
+    int2* __restrict__ hyper,          // [Tpad][M][HS]
+    int32_t T, int32_t Tpad, int32_t M0, int32_t M, int32_t nnz, int32_t d) {
+  const int hs = eif_hyper_stride(nnz);
+  const int64_t total = (int64_t)Tpad * M;
+  for (int64_t g = (int64_t)blockIdx.x * DEEP_BT + threadIdx.x; g < total;
+       g += (int64_t)gridDim.x * DEEP_BT) {
+    const int t = (int)(g / M), i = (int)(g - (int64_t)t * M);
+    const int2 rec = lvl[g];
+    // only the root has pre-order index 0: any other slot that carries it is
+    // one the reorder filled in (past the tree's nodes, or a pad tree)
+    const bool slot = t < T && (i == 0 || rec.y > 0);
+    const bool internal = slot && rec_link(rec.x) != i;
+    const int old = min(max(rec.y, 0), M0 - 1);
+    const int64_t src = (int64_t)t * M0 + old;
+    nodes[g] = make_int2(rec.x, slot ? vw[src] : 0);
+    int2* dst = hyper + g * hs;
+    for (int j = 0; j < hs; ++j)
+      dst[j] = internal && j < nnz
+                   ? make_int2(min(max(hidx[src * nnz + j], 0), d - 1),
+                               hw[src * nnz + j])
+                   : make_int2(0, 0);
+  }
+}
+
+// n 8-byte words from global memory into LDS, all threads of the block; dst
+// is on 16 bytes. The reads are 16-byte pieces from src's first 16-byte
+// boundary on (a tree of an odd M starts on 8), the stores too where src
+// itself is on 16.
+__device__ __forceinline__ void stage_words(int2* dst,
+                                            const int2* __restrict__ src,
+                                            int n) {
+  const int tid = threadIdx.x;
+  const int head = min((int)(((uintptr_t)src >> 3) & 1), n);
+  if (tid < head) dst[0] = src[0];
+  const uint4* s4 = (const uint4*)(src + head);
+  const int pairs = (n - head) >> 1;
+  if (head == 0) {
+    for (int i = tid; i < pairs; i += DEEP_BT) ((uint4*)dst)[i] = s4[i];
+  } else {
+    for (int i = tid; i < pairs; i += DEEP_BT) {
+      const uint4 v = s4[i];
+      dst[1 + 2 * i] = make_int2((int)v.x, (int)v.y);
+      dst[2 + 2 * i] = make_int2((int)v.z, (int)v.w);
+    }
+  }
+  if (((n - head) & 1) && tid == DEEP_BT - 1) dst[n - 1] = src[n - 1];
+}
+
+// The dots of a thread's chains are independent f32 multiplies and adds,
+// which the compiler would pair into packed instructions; this walk keeps
+// one scalar v_mul_f32 / v_add_f32 per term.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DEEP_SCALAR_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define DEEP_SCALAR_F32  // the host pass compiles only the launch stub
+#endif
+
+template <typename XT, int RPT, int PH>
+__global__ void DEEP_SCALAR_F32 __launch_bounds__(DEEP_BT)
+score_extended_deep_kernel(
+    const XT* __restrict__ X,               // raw bf16/fp16/f32 bits
+    const int2* __restrict__ nodes,         // [Tpad][M]
+    const int2* __restrict__ hyper,         // [Tpad][M][HS]
+    const int32_t* __restrict__ lds_levels, // [Tpad]
+    float* __restrict__ out,                // [N] (path sum or score)
+    int64_t N, int32_t d, int32_t nnz, int32_t Tpad, int32_t M, int32_t S,
+    int32_t height, float fT, float c_norm, int32_t finalize, int64_t rs,
+    int64_t cs) {
+  constexpr int FS = RPT * DEEP_BT;
+  constexpr int NC = RPT * PH;  // chain c: row c / PH, tree c % PH
+  constexpr uint32_t ALL = (1u << NC) - 1u;
+  const int tid = threadIdx.x;
+  const int staged = min(S, M);  // records of a tree that the stage holds
+  const int hs = eif_hyper_stride(nnz);
+  const int npair = nnz >> 1;
+
+  int2* hlds = (int2*)smem;                 // [PH][S][HS]
+  int2* tlds = hlds + (size_t)PH * S * hs;  // [PH][S]
+  XT* rows = (XT*)(tlds + PH * S);          // [d][FS]
+
+  for (int64_t block_row0 = (int64_t)blockIdx.x * FS; block_row0 < N;
+       block_row0 += (int64_t)gridDim.x * FS) {
+    const int rows_here = (int)min((int64_t)FS, N - block_row0);
+
+    __syncthreads();  // previous tile's readers done
+    stage_tile<XT, RPT, false>(rows, X, block_row0, rows_here, d, rs, cs);
+    // the first phase's barriers order these stores before the walk
+
+    const XT* rb[RPT];
+#pragma unroll
+    for (int r = 0; r < RPT; ++r)
+      rb[r] = rows + tile_slot<XT, RPT>(tid + r * DEEP_BT);
+
+    float psum[RPT];
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) psum[r] = 0.f;
+
+    for (int t = 0; t < Tpad; t += PH) {
+      __syncthreads();  // previous phase's LDS readers done
+#pragma unroll
+      for (int s = 0; s < PH; ++s) {
+        stage_words(tlds + s * S, nodes + (int64_t)(t + s) * M, staged);
+        stage_words(hlds + (size_t)s * S * hs,
+                    hyper + (int64_t)(t + s) * M * hs, staged * hs);
+      }
+      // trips that stay inside every tree's stage. 0 levels means the root
+      // is a leaf, which rests at record 0 for any number of trips.
+      int la = height;
+#pragma unroll
+      for (int s = 0; s < PH; ++s) {
+        const int l = lds_levels[t + s];
+        if (l > 0) la = min(la, l);
+      }
+      __syncthreads();
+
+      const int2* nbase[PH];
+      const int2* hbase[PH];
+#pragma unroll
+      for (int s = 0; s < PH; ++s) {
+        nbase[s] = nodes + (int64_t)(t + s) * M;
+        hbase[s] = hyper + (int64_t)(t + s) * M * hs;
+      }
+
+      int cur[NC], val[NC];
+#pragma unroll
+      for (int c = 0; c < NC; ++c) cur[c] = val[c] = 0;
+      // bit c of `live`: the chain has not read its leaf yet (phase B)
+      uint32_t live = ALL;
+
+      // One level of the thread's chains. MODE 0: phase A, every record and
+      // entry from LDS, no flags. MODE 1: the first tail trip, from LDS below
+      // S (the level after the staged ones straddles the stage's end, and a
+      // chain may rest at a staged leaf). MODE 2: from global memory.
+      auto trip = [&](auto mode) __attribute__((always_inline)) {
+        constexpr int MODE = decltype(mode)::value;
+        const uint32_t walk = MODE == 0 ? ALL : live;
+        int2 nd[NC];
+        uint32_t in_lds = MODE == 0 ? ALL : 0u;
+        int lo[NC];      // first entry of the node: in the stage,
+        int64_t go[NC];  // in the tree
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+          if (walk & (1u << c)) {
+            const int s = c % PH;
+            if (MODE == 1 && cur[c] < S) in_lds |= 1u << c;
+            if (in_lds & (1u << c)) {
+              nd[c] = tlds[s * S + cur[c]];
+              lo[c] = (s * S + cur[c]) * hs;
+            } else {
+              nd[c] = nbase[s][cur[c]];
+              go[c] = (int64_t)cur[c] * hs;
+            }
+          }
+        float dot[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) dot[c] = 0.f;
+        // `on`: the chain reads an internal node on this trip. The first
+        // entry load of a tail trip does not wait for the record to say so.
+        uint32_t on = 0;
+        for (int j = 0; j < npair; ++j) {
+          const uint32_t ld = (MODE == 0 || j == 0) ? walk : on;
+          int4 p[NC];
+#pragma unroll
+          for (int c = 0; c < NC; ++c)
+            if (ld & (1u << c))
+              p[c] = (in_lds & (1u << c))
+                         ? *(const int4*)(hlds + lo[c] + 2 * j)
+                         : *(const int4*)(hbase[c % PH] + go[c] + 2 * j);
+          XT xa[NC], xb[NC];
+#pragma unroll
+          for (int c = 0; c < NC; ++c)
+            if (ld & (1u << c)) {
+              xa[c] = rb[c / PH][p[c].x * FS];
+              xb[c] = rb[c / PH][p[c].z * FS];
+            }
+#pragma unroll
+          for (int c = 0; c < NC; ++c)
+            if (ld & (1u << c)) {
+              dot[c] = __fadd_rn(dot[c], __fmul_rn(__int_as_float(p[c].y),
+                                                   widen_row(xa[c])));
+              dot[c] = __fadd_rn(dot[c], __fmul_rn(__int_as_float(p[c].w),
+                                                   widen_row(xb[c])));
+            }
+          if (MODE != 0 && j == 0) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c)
+              if ((walk & (1u << c)) && rec_link(nd[c].x) != cur[c])
+                on |= 1u << c;
+          }
+        }
+        if (nnz & 1) {
+          uint32_t ld = walk;
+          if (MODE != 0 && npair > 0) ld = on;
+          int2 p[NC];
+#pragma unroll
+          for (int c = 0; c < NC; ++c)
+            if (ld & (1u << c))
+              p[c] = (in_lds & (1u << c))
+                         ? hlds[lo[c] + nnz - 1]
+                         : hbase[c % PH][go[c] + nnz - 1];
+          XT xa[NC];
+#pragma unroll
+          for (int c = 0; c < NC; ++c)
+            if (ld & (1u << c)) xa[c] = rb[c / PH][p[c].x * FS];
+#pragma unroll
+          for (int c = 0; c < NC; ++c)
+            if (ld & (1u << c))
+              dot[c] = __fadd_rn(dot[c], __fmul_rn(__int_as_float(p[c].y),
+                                                   widen_row(xa[c])));
+        }
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+          if (walk & (1u << c)) {
+            const int link = rec_link(nd[c].x);
+            const bool internal = link != cur[c];
+            if (MODE != 0) {
+              val[c] = nd[c].y;
+              if (!internal) live &= ~(1u << c);
+            }
+            cur[c] = link - (int)(internal &&
+                                  dot[c] < __int_as_float(nd[c].y));
+          }
+      };
+
+      for (int it = 0; it < la; ++it) trip(std::integral_constant<int, 0>{});
+      trip(std::integral_constant<int, 1>{});
+      // a chain at depth `height` is a leaf: height - la more trips read it
+      for (int k = la; k < height && __any(live != 0); ++k)
+        trip(std::integral_constant<int, 2>{});
+
+#pragma unroll
+      for (int r = 0; r < RPT; ++r)
+#pragma unroll
+        for (int s = 0; s < PH; ++s)
+          psum[r] = __fadd_rn(psum[r], __int_as_float(val[r * PH + s]));
+    }
+
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+      const int64_t my_row = block_row0 + tid + r * DEEP_BT;
+      if (my_row < N) {
+        if (finalize) {
+          const float mean32 = (float)((double)psum[r] / (double)fT);
+          const double ratio = (double)mean32 / (double)c_norm;
+          out[my_row] = (float)exp2(-ratio);
+        } else {
+          out[my_row] = psum[r];
+        }
+      }
+    }
+  }
+}
+
 }  // namespace deep
 
 // host-side launchers (bindings.cpp is compiled by g++)
@@ -1075,6 +1371,70 @@ hipError_t launch_explain_extended_deep(
   else LXE(uint32_t);
 #undef LXE
 #undef LXE1
+  return hipGetLastError();
+}
+
+// entries per node of the eif deep pack's hyper array
+int32_t eif_deep_hyper_stride(int32_t nnz) {
+  return deep::eif_hyper_stride(nnz);
+}
+
+// lvl: the int2 records of launch_deep_level_order run with every slot's
+// pre-order index as its threshold word and d = 0
+void launch_eif_score_gather(const void* lvl, const int32_t* vw,
+                             const int32_t* hidx, const int32_t* hw,
+                             void* nodes, void* hyper, int32_t T, int32_t Tpad,
+                             int32_t M0, int32_t M, int32_t nnz, int32_t d,
+                             hipStream_t stream) {
+  const int64_t total = (int64_t)Tpad * M;
+  const int blocks =
+      (int)std::min<int64_t>((total + DEEP_BT - 1) / DEEP_BT, 65535);
+  hipLaunchKernelGGL(deep::eif_score_gather_kernel, dim3(blocks),
+                     dim3(DEEP_BT), 0, stream, (const int2*)lvl, vw, hidx, hw,
+                     (int2*)nodes, (int2*)hyper, T, Tpad, M0, M, nnz, d);
+}
+
+hipError_t launch_score_extended_deep(
+    RowDtype dt, int rpt, int phase, const void* X, const void* nodes,
+    const void* hyper, const int32_t* lds_levels, float* out, int64_t N,
+    int32_t d, int32_t nnz, int64_t rs, int64_t cs, int32_t Tpad, int32_t M,
+    int32_t S, int32_t height, float fT, float c_norm, int finalize,
+    size_t lds, int blocks, hipStream_t stream) {
+  if ((rpt != 1 && rpt != 2) || (phase != 1 && phase != 2 && phase != 4) ||
+      Tpad % phase != 0)
+    return hipErrorInvalidValue;
+  hipError_t err = hipSuccess;
+#define LSE1(XT, RPT, PH)                                                     \
+  do {                                                                        \
+    const void* fn =                                                          \
+        (const void*)deep::score_extended_deep_kernel<XT, RPT, PH>;           \
+    if (lds > 64 * 1024)                                                      \
+      err = hipFuncSetAttribute(                                              \
+          fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
+    if (err != hipSuccess) return err;                                        \
+    hipLaunchKernelGGL((deep::score_extended_deep_kernel<XT, RPT, PH>),       \
+                       dim3(blocks), dim3(DEEP_BT), lds, stream,              \
+                       (const XT*)X, (const int2*)nodes, (const int2*)hyper,  \
+                       lds_levels, out, N, d, nnz, Tpad, M, S, height, fT,    \
+                       c_norm, finalize, rs, cs);                             \
+  } while (0)
+#define LSE2(XT, RPT)                                                         \
+  do {                                                                        \
+    if (phase == 4) LSE1(XT, RPT, 4);                                         \
+    else if (phase == 2) LSE1(XT, RPT, 2);                                    \
+    else LSE1(XT, RPT, 1);                                                    \
+  } while (0)
+#define LSE(XT)                                                               \
+  do {                                                                        \
+    if (rpt == 2) LSE2(XT, 2);                                                \
+    else LSE2(XT, 1);                                                         \
+  } while (0)
+  if (dt == ROW_BF16) LSE(uint16_t);
+  else if (dt == ROW_F16) LSE(deep::f16_t);
+  else LSE(uint32_t);
+#undef LSE
+#undef LSE2
+#undef LSE1
   return hipGetLastError();
 }
 
