@@ -924,6 +924,9 @@ def feature_contributions_extended(fr: ExtendedForest, X: np.ndarray,
 # ---------------------------------------------------------------------------
 
 SHAP_MAX_PATH_FEATURES = 16  # the kernel's c[] holds 17 doubles
+# shap_forest_deep_kernel (forests past the 15-bit node ids): one lane per
+# path feature, at most 32 lanes a row
+SHAP_DEEP_MAX_PATH_FEATURES = 32
 
 
 def shap_weights(max_m: int = SHAP_MAX_PATH_FEATURES) -> np.ndarray:

@@ -970,6 +970,82 @@ def _shap_packed(forest, kind):
     return words, np.ascontiguousarray(tree_off)
 
 
+def _shap_deep_packed(forest, kind):
+    """Deep leaf stream for shap_forest_deep_kernel (layout at the top of
+    ops/hip/shap_kernels.hip) from cpu_engine.shap_tables, for one row kind:
+    per leaf {f64 L, m}, z[m], then for 16-bit rows e[m] = lo16 | hi16 << 16
+    | feature << 32, for f32 rows iv[m] = lo | hi << 32 and ceil(m / 4)
+    words of 16-bit feature ids.
+
+    The intervals are _shap_packed's (§9), but the threshold keys are
+    computed for the path nodes the tables name only: no [T, 2n - 1]
+    temporary. For 16-bit rows the inclusive widened interval [lo, hi] is
+    stored in the domain of the unwidened key k, widen(k) = k << 16 | 0xFFFF:
+    lo <= widen(k) <=> lo >> 16 <= k, widen(k) <= hi <=> k <= (hi - 0xFFFF)
+    >> 16 (negative: no key passes, the empty interval lo16 = 1, hi16 = 0).
+    Returns (words uint64 [W], tree_off int64 [T + 1] in words)."""
+    from ..core.cpu_engine import shap_tables
+
+    kind = _row_kind(kind)
+    tabs = shap_tables(forest)
+    T = forest.num_trees
+    pt, pv = tabs["pn_tree"], tabs["pn_node"]
+    v64 = getattr(forest, "value64", None)
+    splits = types.SimpleNamespace(
+        value=forest.value[pt, pv],
+        value64=None if v64 is None else v64[pt, pv])
+    pn_key = _threshold_keys(_split_thresholds32(splits), kind).astype(
+        np.int64)
+    n_ent = len(tabs["ent_feat"])
+    pn_ent = np.repeat(np.arange(n_ent, dtype=np.int64),
+                       np.diff(tabs["ent_pn_off"]))
+    left = tabs["pn_left"]
+    lo = np.zeros(n_ent, dtype=np.int64)
+    hi = np.full(n_ent, 1 << 32, dtype=np.int64)  # exclusive, none yet
+    np.maximum.at(lo, pn_ent[~left], pn_key[~left])
+    np.minimum.at(hi, pn_ent[left], pn_key[left])
+    never = hi == 0
+    lo[never] = 1
+    hi = np.where(never, 0, hi - 1)  # inclusive
+    feat = tabs["ent_feat"].astype(np.uint64)
+    assert n_ent == 0 or int(feat.max()) <= 4094
+    k16 = kind != "f32"
+    if k16:
+        lo = lo >> 16
+        hi = (hi - 0xFFFF) >> 16
+        never = (hi < lo) | (hi < 0)
+        lo[never], hi[never] = 1, 0
+        ent_word1 = (lo.astype(np.uint64) | (hi.astype(np.uint64)
+                                             << np.uint64(16))
+                     | (feat << np.uint64(32)))
+    else:
+        ent_word1 = lo.astype(np.uint64) | (hi.astype(np.uint64)
+                                            << np.uint64(32))
+
+    leaf_m = tabs["leaf_m"]
+    ent_off = tabs["leaf_ent_off"]
+    n_leaf = len(leaf_m)
+    leaf_words = 2 + 2 * leaf_m + (0 if k16 else (leaf_m + 3) // 4)
+    leaf_word = np.zeros(n_leaf + 1, dtype=np.int64)
+    np.cumsum(leaf_words, out=leaf_word[1:])
+    total = int(leaf_word[-1])
+    words = np.zeros(total, dtype=np.uint64)
+    words[leaf_word[:-1]] = tabs["leaf_L"].view(np.uint64)
+    words[leaf_word[:-1] + 1] = leaf_m.astype(np.uint64)
+    ent_leaf = np.repeat(np.arange(n_leaf, dtype=np.int64), leaf_m)
+    k = np.arange(n_ent, dtype=np.int64) - ent_off[ent_leaf]  # slot in leaf
+    z_word = leaf_word[ent_leaf] + 2 + k
+    words[z_word] = tabs["ent_z"].view(np.uint64)
+    words[z_word + leaf_m[ent_leaf]] = ent_word1
+    if not k16:
+        f_word = leaf_word[ent_leaf] + 2 + 2 * leaf_m[ent_leaf] + k // 4
+        np.bitwise_or.at(words, f_word,
+                         feat << (np.uint64(16) * (k % 4).astype(np.uint64)))
+    tree_off = np.ascontiguousarray(leaf_word[tabs["tree_leaf_off"]])
+    assert tree_off[0] == 0 and tree_off[T] == total
+    return words, tree_off
+
+
 def _eif_packed_wide(forest):
     """Wide int4 node records {is_leaf(-1)/0, right, value_bits, 0} for
     score_extended_wide (strict oracle j-order dot from global
@@ -1411,10 +1487,12 @@ def _device_forest(model, device, v4_key=None):
     the standard-scoring v4 packing; None = the EIF packing. Packs that
     hold integer key thresholds — (d, kind), ("wide", kind),
     ("deep", d, stage, kind), ("eif0", d, kind), ("explain", d, kind),
-    ("explain_deep", d, stage, kind), ("shap", d, kind) — are keyed
+    ("explain_deep", d, stage, kind), ("shap", d, kind),
+    ("shap_deep", d, kind) — are keyed
     on the row KIND, not on "is it 16-bit": bf16 and fp16 keys differ, and
-    u32 records under a u16 kernel score silently wrong. The "shap" entry
-    is (table words, per-tree word offsets, {host offsets, weights}).
+    u32 records under a u16 kernel score silently wrong. The "shap" and
+    "shap_deep" entries are (table words, per-tree word offsets, {host
+    offsets, weights}).
     ("explain_eif_deep", stage) and ("eif_deep", stage) hold f32 offsets and
     weights and serve every row kind."""
     if isinstance(v4_key, tuple) and v4_key[0] not in (
@@ -1525,6 +1603,18 @@ def _device_forest(model, device, v4_key=None):
             ncount = torch.from_numpy(tree_off).to(device)  # word offsets
             extra["tree_off_host"] = torch.from_numpy(tree_off)
             extra["wtab"] = torch.from_numpy(shap_weights()).to(device)
+        elif isinstance(v4_key, tuple) and v4_key[0] == "shap_deep":
+            # ("shap_deep", d, kind): as "shap", the deep leaf stream and
+            # the [33, 32] weights
+            from ..core.cpu_engine import (SHAP_DEEP_MAX_PATH_FEATURES,
+                                           shap_weights)
+
+            words, tree_off = _shap_deep_packed(forest, v4_key[2])
+            aos = torch.from_numpy(words.view(np.int64)).to(device)
+            ncount = torch.from_numpy(tree_off).to(device)  # word offsets
+            extra["tree_off_host"] = torch.from_numpy(tree_off)
+            extra["wtab"] = torch.from_numpy(
+                shap_weights(SHAP_DEEP_MAX_PATH_FEATURES)).to(device)
         elif v4_key == "eif_explain":
             from ..core.cpu_engine import explain_tables
 
@@ -2035,6 +2125,28 @@ def explain_extended_forest(model, X: torch.Tensor,
 # ---------------------------------------------------------------------------
 
 
+def large_shap_route(forest, d: int, dtype) -> str:
+    """Where ``shap_forest`` computes TreeSHAP for a forest past the packed
+    15-bit node ids: ``"deep"`` (shap_forest_deep_kernel: a group of lanes a
+    row, one path feature a lane, the leaf stream from L2) or ``"cpu"`` (the
+    oracle, with a logged warning). ``IFA_SHAP_DEEP=0`` keeps the CPU path;
+    so do extended forests, node arrays that fit the packed formats' 32767
+    (a cap on feature ids alone sent them here), forests past
+    ``DEEP_MAX_NODES`` nodes a tree or 4094 features, and a path that merges
+    more than ``cpu_engine.SHAP_DEEP_MAX_PATH_FEATURES`` features. The kernel
+    keys rows of any width, so ``dtype`` does not move the answer."""
+    from ..core import cpu_engine
+
+    _row_kind(dtype)
+    if os.environ.get("IFA_SHAP_DEEP", "1") == "0":
+        return "cpu"
+    if forest.feature.shape[1] <= 32767 or not _deep_fits(forest, d):
+        return "cpu"
+    max_m = cpu_engine.shap_tables(forest)["max_m"]
+    return ("deep" if max_m <= cpu_engine.SHAP_DEEP_MAX_PATH_FEATURES
+            else "cpu")
+
+
 def _shap_on_cpu(forest, X: torch.Tensor, finalize: bool, why: str):
     """CPU oracle, result moved to X's device (a correctness path)."""
     from ..core import cpu_engine
@@ -2057,15 +2169,36 @@ def shap_forest(model, X: torch.Tensor, finalize: bool = True) -> torch.Tensor:
     if X.dtype not in (torch.float32, torch.bfloat16, torch.float16):
         raise ValueError("shap_values expects float32, bfloat16 or float16 "
                          f"rows on the GPU, got {X.dtype}")
-    fmax = int(forest.feature.max(initial=-1))
+    # wide arrays (2n - 1 columns past the 15-bit ids): the cached maximum
+    fmax = (_feature_max(forest) if forest.feature.shape[1] > 32767
+            else int(forest.feature.max(initial=-1)))
     if fmax >= d:
         raise ValueError(
             f"the forest splits on feature {fmax} but rows have {d} columns")
     if not _packed_fits(forest, d):
-        return _shap_on_cpu(
-            forest, X, finalize,
-            "forest exceeds the packed node format (15-bit node ids, "
-            "12-bit feature ids)")
+        kind = _row_kind(X.dtype)
+        if large_shap_route(forest, d, kind) != "deep":
+            return _shap_on_cpu(
+                forest, X, finalize,
+                "forest exceeds the packed node format (15-bit node ids, "
+                "12-bit feature ids) and the deep route's caps "
+                f"({cpu_engine.SHAP_DEEP_MAX_PATH_FEATURES} features on a "
+                "path)")
+        max_m = cpu_engine.shap_tables(forest)["max_m"]
+        ext = load_extension()
+        if (os.environ.get("IFA_SHAP_DEEP_SPLIT") == "row"
+                and max_m <= cpu_engine.SHAP_MAX_PATH_FEATURES):
+            # A/B only: one row per thread, the table read from global memory
+            table, tree_off, extra = _device_forest(
+                model, X.device, v4_key=("shap", d, kind))
+            return ext.shap_forest(
+                _rows_in_place(X), table, extra["tree_off_host"], tree_off,
+                extra["wtab"], finalize)
+        table, tree_off, extra = _device_forest(
+            model, X.device, v4_key=("shap_deep", d, kind))
+        return ext.shap_forest_deep(
+            _rows_in_place(X), table, extra["tree_off_host"], tree_off,
+            extra["wtab"], max_m, finalize)
     max_m = cpu_engine.shap_tables(forest)["max_m"]
     if max_m > cpu_engine.SHAP_MAX_PATH_FEATURES:
         return _shap_on_cpu(

@@ -188,6 +188,13 @@ void launch_shap_forest(RowDtype dt, bool table_lds, bool acc_lds,
                         int64_t rs, int64_t cs, int32_t T, int32_t table_words,
                         int rows_lds, int finalize, size_t lds, int blocks,
                         hipStream_t stream);
+void launch_shap_forest_deep(RowDtype dt, int G, bool acc_lds, const void* X,
+                             const void* table, const int64_t* tree_off,
+                             const double* wtab, double* acc_g, float* out,
+                             int64_t N, int32_t d, int64_t rs, int64_t cs,
+                             int32_t T, int keys_lds, int32_t stride,
+                             int finalize, size_t lds, int blocks,
+                             hipStream_t stream);
 
 // deep_kernels.hip
 void launch_deep_level_order(const int32_t* feat, const int32_t* right,
@@ -2298,6 +2305,113 @@ torch::Tensor shap_forest(torch::Tensor X, torch::Tensor table,
   return out;
 }
 
+// Entry-parallel TreeSHAP for forests past the 15-bit node ids
+// (shap_forest_deep_kernel): what one call runs, from shapes alone. G lanes
+// own a row (the smallest of 8, 16, 32 that holds max_m), a block 256 / G
+// rows. The 150 KB budget takes the weights, then the key tile, then the
+// float64 accumulator tile whenever it still fits (a tile of 8-32 rows is
+// small: no second block is given up for it as in shap_forest).
+struct ShapDeepCfg {
+  int G;
+  bool acc_lds, keys_lds;
+  int32_t stride;  // row stride of both tiles, in cells
+  size_t lds;
+};
+
+constexpr int kShapDeepMaxM = 32;
+
+ShapDeepCfg pick_shap_deep_cfg(int elem, int64_t d, int64_t max_m) {
+  ShapDeepCfg c;
+  c.G = max_m <= 8 ? 8 : max_m <= 16 ? 16 : 32;
+  const size_t rows = 256 / c.G;
+  c.stride = (int32_t)(d | 1);
+  const size_t budget = 150 * 1024;
+  const size_t wtab_b = (size_t)(kShapDeepMaxM + 1) * kShapDeepMaxM * 8;
+  const size_t keys_b = align16(rows * (size_t)c.stride * (size_t)elem);
+  const size_t acc_b = rows * (size_t)c.stride * 8;
+  c.keys_lds = wtab_b + keys_b <= budget;
+  c.acc_lds = c.keys_lds && wtab_b + keys_b + acc_b <= budget;
+  if (const char* e = getenv("IFA_SHAP_FORCE_GLOBAL_ACC"))
+    if (atoi(e)) c.acc_lds = false;
+  c.lds = wtab_b + (c.acc_lds ? acc_b : 0) + (c.keys_lds ? keys_b : 0);
+  return c;
+}
+
+// (G, accumulators in LDS, keys in LDS) of shap_forest_deep for these shapes
+std::tuple<int64_t, bool, bool> shap_deep_cfg(const std::string& dtype,
+                                              int64_t d, int64_t max_m) {
+  TORCH_CHECK(d >= 1 && d <= 4094, "shap supports 1 <= d <= 4094");
+  TORCH_CHECK(max_m >= 0 && max_m <= kShapDeepMaxM,
+              "the deep shap kernel holds at most 32 features on a path");
+  const ShapDeepCfg c = pick_shap_deep_cfg(elem_bytes_of(dtype), d, max_m);
+  return {c.G, c.acc_lds, c.keys_lds};
+}
+
+// `table` is the deep leaf stream of gpu_engine._shap_deep_packed for X's row
+// kind (layout in shap_kernels.hip), `tree_off` as in shap_forest, `wtab`
+// cpu_engine.shap_weights(32), `max_m` the most features any path merges.
+torch::Tensor shap_forest_deep(torch::Tensor X, torch::Tensor table,
+                               torch::Tensor tree_off_host,
+                               torch::Tensor tree_off, torch::Tensor wtab,
+                               int64_t max_m, bool finalize) {
+  CHECK_CUDA(X);
+  CHECK_CUDA(table);
+  CHECK_CONTIG(table);
+  CHECK_CUDA(tree_off);
+  CHECK_CONTIG(tree_off);
+  CHECK_CUDA(wtab);
+  CHECK_CONTIG(wtab);
+  CHECK_CONTIG(tree_off_host);
+  check_x(X);
+  const XLayout xl = check_x_layout(X);
+  TORCH_CHECK(table.dim() == 1 && table.scalar_type() == torch::kInt64,
+              "table must be the int64 word stream");
+  TORCH_CHECK(!tree_off_host.is_cuda() && tree_off_host.dim() == 1 &&
+                  tree_off_host.scalar_type() == torch::kInt64 &&
+                  tree_off_host.size(0) >= 2,
+              "tree_off_host must be a host int64 [T + 1]");
+  TORCH_CHECK(tree_off.dim() == 1 && tree_off.scalar_type() == torch::kInt64 &&
+                  tree_off.size(0) == tree_off_host.size(0),
+              "tree_off must be int64 [T + 1] like tree_off_host");
+  TORCH_CHECK(wtab.scalar_type() == torch::kFloat64 &&
+                  wtab.numel() == (kShapDeepMaxM + 1) * kShapDeepMaxM,
+              "wtab must be float64 [33, 32]");
+  TORCH_CHECK(max_m >= 0 && max_m <= kShapDeepMaxM,
+              "the deep shap kernel holds at most 32 features on a path");
+  const int64_t N = X.size(0), d = X.size(1);
+  const int64_t T = tree_off_host.size(0) - 1;
+  const int64_t* to = tree_off_host.data_ptr<int64_t>();
+  TORCH_CHECK(to[0] == 0 && to[T] == table.numel(),
+              "tree_off must span the table exactly");
+  for (int64_t t = 0; t < T; ++t)  // per-tree word counts are int32
+    TORCH_CHECK(to[t + 1] >= to[t] + 2 && to[t + 1] - to[t] < (int64_t)1 << 31,
+                "tree_off must grow by 2 words to 2^31 - 1 words a tree");
+  TORCH_CHECK(d >= 1 && d <= 4094, "shap supports 1 <= d <= 4094");
+  const auto out_opts = X.options().dtype(torch::kFloat32);
+  if (N == 0) return torch::empty({N, d}, out_opts);
+
+  const ifa::RowDtype dt = row_dtype(X);
+  const ShapDeepCfg c = pick_shap_deep_cfg(ifa::row_elem_bytes(dt), d, max_m);
+  auto out = torch::empty({N, d}, out_opts);
+  torch::Tensor acc_g;
+  if (!c.acc_lds)
+    acc_g = torch::zeros({N, d}, X.options().dtype(torch::kFloat64));
+  int64_t max_blocks = 8192;
+  if (const char* e = getenv("IFA_SHAP_MAX_BLOCKS")) {
+    const int64_t v = atoll(e);
+    if (v >= 1) max_blocks = std::min<int64_t>(v, 8192);
+  }
+  const int64_t rows = 256 / c.G;
+  const int blocks = (int)std::min<int64_t>((N + rows - 1) / rows, max_blocks);
+  ifa::launch_shap_forest_deep(
+      dt, c.G, c.acc_lds, X.data_ptr(), table.data_ptr<int64_t>(),
+      tree_off.data_ptr<int64_t>(), wtab.data_ptr<double>(),
+      c.acc_lds ? nullptr : acc_g.data_ptr<double>(), out.data_ptr<float>(), N,
+      (int32_t)d, xl.rs, xl.cs, (int32_t)T, c.keys_lds ? 1 : 0, c.stride,
+      finalize ? 1 : 0, c.lds, blocks, current_stream());
+  return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bag_gather", &bag_gather, "gather per-tree bags (K9/K10)");
   m.def("bag_sample_lds", &bag_sample_lds,
@@ -2368,6 +2482,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-feature path-length attribution, extended forests");
   m.def("shap_forest", &shap_forest,
         "exact path-dependent TreeSHAP values, standard forests");
+  m.def("shap_deep_cfg", &shap_deep_cfg,
+        "(lanes per row G, accumulators in LDS, keys in LDS) of "
+        "shap_forest_deep for (dtype, d, max_m)");
+  m.def("shap_forest_deep", &shap_forest_deep,
+        "exact TreeSHAP past 15-bit node ids: G lanes a row, one entry a lane");
   m.def("deep_stage", &deep_stage,
         "records per tree score_forest_deep stages for (dtype, d); 0: none");
   m.def("deep_level_order", &deep_level_order,

@@ -38,6 +38,41 @@
 // This TU is torch-free and stands alone: the few key helpers it shares with
 // forest_kernels.hip are duplicated here (namespace ifa::shap) so that the
 // other TU's code, and the native scorer that links only it, do not change.
+//
+// Forests past the 15-bit node ids: shap_forest_deep_kernel<KT, G, ACC_LDS>.
+// Same contract, same bits, another split of the work: a tree of a large bag
+// has thousands of leaves and TreeSHAP is asked for few rows, so a group of
+// G consecutive lanes (8, 16 or 32, the smallest >= the forest's max_m) owns
+// one row and lane a of the group computes entry a's term of the leaf; a
+// 256-thread block holds 256 / G rows. Within a leaf the m entries have
+// distinct features: the m adds go to m different accumulator cells, and
+// every lane runs exactly the contract's operations for its own a, in the
+// contract's order. The block still walks the stream in lockstep (L, m and
+// every z_b are uniform reads); lane a reads only its own entry's interval
+// and one key, a ballot gives the group its o bits. Lanes a >= m compute
+// along on entry m - 1 and add nothing.
+//
+// Deep table stream (gpu_engine._shap_deep_packed), 8-byte words, trees back
+// to back, leaves in ascending node id, entry arrays split so that the lanes
+// of a group read consecutive words:
+//   { f64 L , m }
+//   z[m]                                      f64
+//   16-bit rows: e[m] = lo16 | hi16 << 16 | feature << 32
+//   f32 rows   : iv[m] = lo | hi << 32, then ceil(m / 4) words of features,
+//                16 bits each, entry k in word k / 4 at bit 16 * (k % 4)
+// A single-leaf tree is the two header words with m = 0. For 16-bit rows
+// [lo16, hi16] is the same inclusive interval in the domain of the unwidened
+// 16-bit key (widen(k) = k << 16 | 0xFFFF is monotone, so lo <= widen(k) <=
+// hi <=> lo >> 16 <= k <= (hi - 0xFFFF) >> 16; the empty interval stays
+// lo16 = 1, hi16 = 0, and hi16 = 0xFFFF admits the NaN key).
+// The stream is read from global memory (L2) at uniform addresses: a tree's
+// table is megabytes. LDS: the Shapley weights [33][32], the float64
+// accumulator tile [rows][d | 1] when ACC_LDS (the odd stride spreads the
+// groups of a wave over the banks; else the pre-zeroed global scratch [N][d],
+// group-owned), the key tile [rows][d | 1] when keys_lds (else keyed from X
+// per use). A group lives in one wave, so a row's accumulator cells are only
+// ever touched by that wave, in program order: the tree loop needs no
+// barrier.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -245,6 +280,179 @@ __global__ void __launch_bounds__(256) shap_forest_kernel(
   }
 }
 
+#define IFA_SHAP_DEEP_MAXM 32
+
+__device__ __forceinline__ double word_f64(uint64_t w) {
+  return __longlong_as_double((long long)w);
+}
+
+// unwidened key of a 16-bit row cell / the key of an f32 cell, as u32
+__device__ __forceinline__ uint32_t cell_key(uint16_t b) {
+  return (uint32_t)key_of_bits<uint16_t>(b);
+}
+__device__ __forceinline__ uint32_t cell_key(f16_t b) {
+  return (uint32_t)(uint16_t)key_of_bits<f16_t>(b);
+}
+__device__ __forceinline__ uint32_t cell_key(uint32_t b) { return key32(b); }
+
+template <typename KT, int G, bool ACC_LDS>
+__global__ void __launch_bounds__(256) shap_forest_deep_kernel(
+    const KT* __restrict__ X,               // raw bf16/fp16/f32 bits
+    const uint64_t* __restrict__ table,     // deep leaf stream (see the top)
+    const int64_t* __restrict__ tree_off,   // [T + 1], in words
+    const double* __restrict__ wtab_g,      // [33][32] Shapley weights
+    double* __restrict__ acc_g,             // [N][d] pre-zeroed (!ACC_LDS)
+    float* __restrict__ out,                // [N][d]
+    int64_t N, int32_t d, int32_t T, int32_t keys_lds, int32_t stride,
+    double dT, int32_t finalize, int64_t rs, int64_t cs) {
+  constexpr int R = 256 / G;  // rows per block
+  constexpr bool K16 = sizeof(KT) == 2;
+  const int tid = threadIdx.x;
+  const int a = tid & (G - 1);          // this lane's entry
+  const int r = tid / G;                // this lane's row of the tile
+  const int gbase = (tid & 63) & ~(G - 1);  // the group's first lane in the wave
+
+  // LDS carve-up, 8-byte items first; `stride` = d | 1 for both tiles
+  double* wtab = (double*)smem;  // [33][32]
+  double* acc = wtab + (IFA_SHAP_DEEP_MAXM + 1) * IFA_SHAP_DEEP_MAXM;
+  KT* keys = (KT*)(acc + (ACC_LDS ? R * stride : 0));
+
+  for (int i = tid; i < (IFA_SHAP_DEEP_MAXM + 1) * IFA_SHAP_DEEP_MAXM;
+       i += 256)
+    wtab[i] = wtab_g[i];
+
+  for (int64_t row0 = (int64_t)blockIdx.x * R; row0 < N;
+       row0 += (int64_t)gridDim.x * R) {
+    const int rows_here = (int)min((int64_t)R, N - row0);
+    const int64_t my_row = row0 + r;
+    const bool live = r < rows_here;
+
+    __syncthreads();  // previous tile's flush done
+    if (keys_lds) {
+      const uint32_t total = (uint32_t)rows_here * (uint32_t)d;
+      if (rs == 1) {  // feature-major source: rows run fastest
+        for (uint32_t g = tid; g < total; g += 256) {
+          const int c = (int)(g / (uint32_t)rows_here);
+          const int rr = (int)(g % (uint32_t)rows_here);
+          keys[rr * stride + c] =
+              key_of_bits<KT>(X[(row0 + rr) + (int64_t)c * cs]);
+        }
+      } else {
+        for (uint32_t g = tid; g < total; g += 256) {
+          const int rr = (int)(g / (uint32_t)d), c = (int)(g % (uint32_t)d);
+          keys[rr * stride + c] =
+              key_of_bits<KT>(X[(row0 + rr) * rs + (int64_t)c * cs]);
+        }
+      }
+      // rows past the end of a short tile: any defined key will do, their
+      // groups compute along and store nothing
+      for (int g = rows_here * stride + tid; g < R * stride; g += 256)
+        keys[g] = (KT)0;
+    }
+    if (ACC_LDS)
+      for (int g = tid; g < R * stride; g += 256) acc[g] = 0.0;
+    __syncthreads();  // tiles staged
+
+    for (int t = 0; t < T; ++t) {
+      const int64_t w0 = tree_off[t];
+      const int nwords = (int)(tree_off[t + 1] - w0);
+      const uint64_t* tb = table + w0;
+
+      int p = 0;
+      while (p < nwords) {  // leaves, ascending node id
+        const double L = word_f64(tb[p]);
+        const int m = (int)(uint32_t)tb[p + 1];
+        const uint64_t* zs = tb + p + 2;   // z[m]
+        const uint64_t* es = zs + m;       // e[m] / iv[m]
+        p += 2 + 2 * m + (K16 ? 0 : (m + 3) >> 2);
+        if (m == 0) continue;  // single-leaf tree (uniform)
+
+        // this lane's entry: interval, feature, one key of the row
+        const int am = min(a, m - 1);
+        const uint64_t e = es[am];
+        uint32_t lo, hi;
+        int fa;
+        if (K16) {
+          lo = (uint32_t)e & 0xFFFFu;
+          hi = ((uint32_t)e >> 16) & 0xFFFFu;
+          fa = (int)(uint32_t)(e >> 32);
+        } else {
+          lo = (uint32_t)e;
+          hi = (uint32_t)(e >> 32);
+          fa = (int)((es[m + (am >> 2)] >> (16 * (am & 3))) & 0xFFFFu);
+        }
+        uint32_t key;
+        if (keys_lds) {
+          key = K16 ? (uint32_t)(uint16_t)keys[r * stride + fa]
+                    : (uint32_t)keys[r * stride + fa];
+        } else {
+          key = live ? cell_key(X[my_row * rs + (int64_t)fa * cs]) : 0u;
+        }
+        const bool o = lo <= key && key <= hi;
+        const uint32_t omask = (uint32_t)(__ballot(o) >> gbase) &
+                               (uint32_t)((1ull << m) - 1ull);
+
+        // the contract's recurrence for entry a: step s meets b = s + (s >= a)
+        double c[G];
+        c[0] = 1.0;
+#pragma unroll
+        for (int k = 1; k < G; ++k) c[k] = 0.0;
+        double z0 = word_f64(zs[0]);
+        for (int s = 0; s < m - 1; ++s) {  // cnt = s, uniform
+          const double z1 = word_f64(zs[s + 1]);
+          const bool past = s >= a;
+          const double zb = past ? z1 : z0;
+          const bool ob = (omask >> (s + (past ? 1 : 0))) & 1u;
+#pragma unroll
+          for (int k = G - 2; k >= 0; --k) {
+            if (k <= s) {  // uniform
+              const double sum = __dadd_rn(c[k + 1], c[k]);
+              c[k + 1] = ob ? sum : c[k + 1];
+              c[k] = __dmul_rn(c[k], zb);
+            }
+          }
+          z0 = z1;
+        }
+        double W = 0.0;
+        const double* wm = wtab + m * IFA_SHAP_DEEP_MAXM;
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+          if (k < m) W = __dadd_rn(W, __dmul_rn(c[k], wm[k]));  // uniform
+
+        const double za = word_f64(zs[am]);
+        const double oa = ((omask >> am) & 1u) ? 1.0 : 0.0;
+        const double term = __dmul_rn(__dmul_rn(L, __dsub_rn(oa, za)), W);
+        if (a < m) {
+          if (ACC_LDS) {
+            double* q = acc + r * stride + fa;
+            *q = __dadd_rn(*q, term);
+          } else if (live) {
+            double* q = acc_g + my_row * d + fa;
+            *q = __dadd_rn(*q, term);
+          }
+        }
+      }
+    }
+
+    if (ACC_LDS) {
+      __syncthreads();  // every row's accumulators final
+      const uint32_t total = (uint32_t)rows_here * (uint32_t)d;
+      for (uint32_t g = tid; g < total; g += 256) {
+        const int rr = (int)(g / (uint32_t)d), c = (int)(g % (uint32_t)d);
+        const double v = acc[rr * stride + c];
+        out[(row0 + rr) * d + c] = finalize ? (float)(v / dT) : (float)v;
+      }
+    } else {
+      // the group's own cells, written by these lanes above
+      if (live)
+        for (int c = a; c < d; c += G) {
+          const double v = acc_g[my_row * d + c];
+          out[my_row * d + c] = finalize ? (float)(v / dT) : (float)v;
+        }
+    }
+  }
+}
+
 }  // namespace shap
 
 // host-side launcher (bindings.cpp is compiled by g++)
@@ -279,6 +487,44 @@ void launch_shap_forest(RowDtype dt, bool table_lds, bool acc_lds,
   else LSH(uint32_t);
 #undef LSH
 #undef LSH1
+}
+
+// G: lanes per row (8, 16 or 32); stride: the tiles' row stride in cells
+void launch_shap_forest_deep(RowDtype dt, int G, bool acc_lds, const void* X,
+                             const void* table, const int64_t* tree_off,
+                             const double* wtab, double* acc_g, float* out,
+                             int64_t N, int32_t d, int64_t rs, int64_t cs,
+                             int32_t T, int keys_lds, int32_t stride,
+                             int finalize, size_t lds, int blocks,
+                             hipStream_t stream) {
+#define LSD1(KT, GG, AL)                                                      \
+  do {                                                                        \
+    if (lds > 64 * 1024)                                                      \
+      (void)hipFuncSetAttribute(                                              \
+          (const void*)shap::shap_forest_deep_kernel<KT, GG, AL>,             \
+          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
+    hipLaunchKernelGGL((shap::shap_forest_deep_kernel<KT, GG, AL>),           \
+                       dim3(blocks), dim3(256), lds, stream, (const KT*)X,    \
+                       (const uint64_t*)table, tree_off, wtab, acc_g, out, N, \
+                       d, T, keys_lds, stride, (double)T, finalize, rs, cs);  \
+  } while (0)
+#define LSD2(KT, GG)                                                          \
+  do {                                                                        \
+    if (acc_lds) LSD1(KT, GG, true);                                          \
+    else LSD1(KT, GG, false);                                                 \
+  } while (0)
+#define LSD(KT)                                                               \
+  do {                                                                        \
+    if (G == 8) LSD2(KT, 8);                                                  \
+    else if (G == 16) LSD2(KT, 16);                                           \
+    else LSD2(KT, 32);                                                        \
+  } while (0)
+  if (dt == ROW_BF16) LSD(uint16_t);
+  else if (dt == ROW_F16) LSD(shap::f16_t);
+  else LSD(uint32_t);
+#undef LSD
+#undef LSD2
+#undef LSD1
 }
 
 }  // namespace ifa
