@@ -184,9 +184,13 @@ class ExtendedForest:
         )
 
     def invalidate_derived(self):
-        """See Forest.invalidate_derived."""
+        """See Forest.invalidate_derived. Also drops what gpu_engine has
+        read off the hyperplanes to route a call (coordinate range and
+        order, uniform width)."""
         self.__dict__.pop("_explain_tables", None)
         self.__dict__.pop("_shap_tables", None)
+        for name in ("_coord_range", "_coords_ascending", "_uniform_nnz"):
+            self.__dict__.pop(name, None)
 
     def leaf_values_from_counts(self):
         self.invalidate_derived()

@@ -1304,6 +1304,49 @@ def _nodes_packed(forest) -> np.ndarray:
     return packed
 
 
+def _eif_explain_dense_packed(forest, D: int):
+    """The ("eif_explain_dense", D) pack of explain_extended_dense_kernel
+    (ops/hip/explain_kernels.hip), for forests extended_explain_route calls
+    "dense" (every internal node nnz distinct coordinates below D):
+
+    * nodes int32 [T, mn, 2]: right | slot << 16 and the f32 offset bits,
+      slot being the node's rank among its tree's internal nodes; leaves and
+      pads hold their own id and 0;
+    * rows float32 [T, MI, 3, D]: per slot the hyperplane weights and the
+      delta_left / delta_right shares of cpu_engine.explain_tables, scattered
+      to their coordinates' columns (copies, nothing recomputed); every
+      other column is +0.0;
+    * ncount, icount int32 [T] (live records, internal nodes) and the
+      forest's height."""
+    from ..core.cpu_engine import explain_tables
+
+    tabs = explain_tables(forest)
+    feat = forest.feature
+    T, mn = feat.shape
+    internal = feat >= 0
+    live = internal | (feat == ExtendedForest.LEAF)
+    slot = np.cumsum(internal, axis=1, dtype=np.int32) - 1
+    icount = internal.sum(axis=1).astype(np.int32)
+    ids = np.broadcast_to(np.arange(mn, dtype=np.int32)[None, :], (T, mn))
+    nodes = np.empty((T, mn, 2), dtype=np.int32)
+    nodes[..., 0] = np.where(
+        internal, forest.right.astype(np.int32) | (slot << 16), ids)
+    nodes[..., 1] = np.where(internal, forest.value.view(np.int32), 0)
+    rows = np.zeros((T, max(int(icount.max(initial=0)), 1), 3, D),
+                    dtype=np.float32)
+    ti, vi = np.nonzero(internal)
+    at = (ti[:, None], slot[ti, vi][:, None])
+    cols = forest.hyper_idx[ti, vi].astype(np.int64)
+    rows[at + (0, cols)] = forest.hyper_w[ti, vi]
+    rows[at + (1, cols)] = tabs["dl"][ti, vi]
+    rows[at + (2, cols)] = tabs["dr"][ti, vi]
+    depth = _node_depths(feat, forest.right)
+    max_depth = int(depth[live].max()) if live.any() else 0
+    return (nodes, rows,
+            np.ascontiguousarray(forest.node_count, dtype=np.int32), icount,
+            max_depth)
+
+
 _TWO32 = 1 << 32
 _TWO31 = 1 << 31
 
@@ -1493,10 +1536,12 @@ def _device_forest(model, device, v4_key=None):
     u32 records under a u16 kernel score silently wrong. The "shap" and
     "shap_deep" entries are (table words, per-tree word offsets, {host
     offsets, weights}).
-    ("explain_eif_deep", stage) and ("eif_deep", stage) hold f32 offsets and
-    weights and serve every row kind."""
+    ("explain_eif_deep", stage), ("eif_deep", stage) and
+    ("eif_explain_dense", D) hold f32 offsets and weights and serve every
+    row kind."""
     if isinstance(v4_key, tuple) and v4_key[0] not in (
-            "eif_dense", "eif_dense3", "explain_eif_deep", "eif_deep"):
+            "eif_dense", "eif_dense3", "explain_eif_deep", "eif_deep",
+            "eif_explain_dense"):
         v4_key = v4_key[:-1] + (_row_kind(v4_key[-1]),)
     key = (str(device), id(model.forest), v4_key)
     cache = model._gpu_forest_cache
@@ -1629,6 +1674,17 @@ def _device_forest(model, device, v4_key=None):
                 np.ascontiguousarray(forest.hyper_w)).to(device)
             extra["dl"] = torch.from_numpy(tabs["dl"]).to(device)
             extra["dr"] = torch.from_numpy(tabs["dr"]).to(device)
+        elif isinstance(v4_key, tuple) and v4_key[0] == "eif_explain_dense":
+            # ("eif_explain_dense", D): aos = the node records, ncount =
+            # live records a tree, extra["rows"] = the dense weight and
+            # share rows, extra["icount"] = internal nodes a tree
+            nodes, rows, nc, ic, max_depth = _eif_explain_dense_packed(
+                forest, v4_key[1])
+            aos = torch.from_numpy(nodes).to(device)
+            ncount = torch.from_numpy(nc).to(device)
+            extra["rows"] = torch.from_numpy(rows).to(device)
+            extra["icount"] = torch.from_numpy(ic).to(device)
+            extra["height"] = max_depth
         elif isinstance(v4_key, tuple) and v4_key[0] == "wide":
             packed, max_depth = _nodes_packed_wide(forest, v4_key[1])
             aos = torch.from_numpy(packed).to(device)
@@ -2035,6 +2091,75 @@ def large_explain_route(forest, d: int, dtype) -> str:
     return "deep" if _explain_deep_stage(_row_kind(dtype), d) > 0 else "cpu"
 
 
+# Narrowest hyperplane (coordinates a node) that extended_explain_route sends
+# to the dense kernel when nnz < d. Measured at d = 32, the widest rows the
+# kernel takes: the smallest of nnz 2, 6 and 16 at which it beats the strict
+# kernel, and it does at all three (profiles/explain_eif_dense.md).
+EIF_EXPLAIN_DENSE_MIN_NNZ = 2
+
+
+def _eif_coords_ascending(forest) -> bool:
+    """True when every internal node of an extended forest carries exactly
+    forest.nnz coordinates in strictly ascending order (so they are distinct,
+    and a dot over dense columns adds its terms in the oracle's order);
+    cached on the forest like _coord_range, dropped by invalidate_derived().
+    Forests built here always do; foreign files may not."""
+    ok = getattr(forest, "_coords_ascending", None)
+    if ok is None:
+        internal = forest.feature >= 0
+        ok = True
+        if internal.any():
+            idx = forest.hyper_idx[internal]
+            ok = bool((forest.feature[internal] == forest.nnz).all()
+                      and (idx[:, 1:] > idx[:, :-1]).all())
+        forest._coords_ascending = ok
+    return ok
+
+
+def _explain_eif_dense_cfg(kind: str, d: int, max_nodes: int):
+    """(D, rows per thread, trees per phase, block threads) the dense EIF
+    explain kernel runs these rows with against node arrays this wide, zeros
+    where it has no instantiation or a tree's stage does not fit in LDS; see
+    _deep_stage."""
+    from . import load_extension as _packing_extension
+
+    return tuple(int(v) for v in _packing_extension().explain_eif_dense_cfg(
+        kind, int(d), int(max_nodes)))
+
+
+def extended_explain_route(forest, d: int, dtype) -> str:
+    """Where ``explain_extended_forest`` attributes an extended forest:
+
+    * ``"dense"`` (explain_extended_dense_kernel: the whole tree staged in
+      LDS as dense weight and share rows, rows and accumulators in
+      registers) for a forest inside the packed caps with ``d <= 32``,
+      every internal node holding ``nnz`` strictly ascending coordinates
+      below ``d``, ``nnz == d`` or ``nnz >= EIF_EXPLAIN_DENSE_MIN_NNZ``, and
+      a tree's stage fitting in LDS (maxSamples 256 does at every such d);
+    * ``"strict"`` (explain_extended_kernel, one thread a row from global
+      memory) for every other forest inside the packed caps, and for all of
+      them under ``IFA_EXPLAIN_EIF_DENSE=0``;
+    * past the packed caps, ``large_explain_route``'s ``"deep"`` or
+      ``"cpu"``.
+
+    With ``nnz < d`` the dense kernel multiplies unselected cells by a zero
+    weight, so ``explain_extended_forest`` sends a batch there only when all
+    of its cells are finite; the strict kernel takes the others. All routes
+    return the same bits."""
+    if not _packed_fits(forest, d):
+        return large_explain_route(forest, d, dtype)
+    if os.environ.get("IFA_EXPLAIN_EIF_DENSE", "1") == "0" or d > 32:
+        return "strict"
+    nnz = forest.nnz
+    if nnz != d and nnz < EIF_EXPLAIN_DENSE_MIN_NNZ:
+        return "strict"
+    cmin, cmax = _coord_range(forest)
+    if cmin < 0 or cmax >= d or not _eif_coords_ascending(forest):
+        return "strict"
+    cfg = _explain_eif_dense_cfg(_row_kind(dtype), d, forest.feature.shape[1])
+    return "dense" if cfg[0] > 0 else "strict"
+
+
 def _explain_on_cpu(fn, forest, X: torch.Tensor, finalize: bool, why: str):
     """Forests past the packed-record caps that the deep explain route does
     not take either: CPU oracle, result moved to X's device (a correctness
@@ -2089,7 +2214,8 @@ def explain_extended_forest(model, X: torch.Tensor,
                             finalize: bool = True) -> torch.Tensor:
     """EIF contributions [N, d] float32 on X's device, bitwise equal to
     cpu_engine.feature_contributions_extended at every extension level
-    (one strict-order kernel for forests inside the packed caps; past them
+    (inside the packed caps the dense register-resident kernel or the
+    strict-order one, see extended_explain_route; past them
     explain_extended_deep, see large_explain_route)."""
     from ..core import cpu_engine
 
@@ -2114,6 +2240,18 @@ def explain_extended_forest(model, X: torch.Tensor,
             "forest exceeds the packed node format (15-bit node ids, "
             "12-bit hyperplane widths)")
     ext = load_extension()
+    # a zero weight times a non-finite cell is NaN where the oracle never
+    # reads that cell: nnz < d goes dense with finite batches only (the
+    # guard of score_extended_forest); nnz == d has no zero column
+    if (extended_explain_route(forest, d, X.dtype) == "dense"
+            and (forest.nnz == d or bool(torch.isfinite(X).all().item()))):
+        D = _explain_eif_dense_cfg(_row_kind(X.dtype), d,
+                                   forest.feature.shape[1])[0]
+        nodes, ncount, extra = _device_forest(
+            model, X.device, v4_key=("eif_explain_dense", D))
+        return ext.explain_extended_dense(
+            _rows_in_place(X), nodes, extra["rows"], ncount, extra["icount"],
+            extra["height"], finalize)
     aos, ncount, extra = _device_forest(model, X.device, v4_key="eif_explain")
     return ext.explain_extended_forest(
         _rows_in_place(X), aos, extra["hidx"], extra["hw"], extra["dl"],

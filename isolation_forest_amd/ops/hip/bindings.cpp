@@ -249,6 +249,16 @@ hipError_t launch_score_extended_deep(
     int32_t S, int32_t height, float fT, float c_norm, int finalize,
     size_t lds, int blocks, hipStream_t stream);
 
+// explain_kernels.hip
+void explain_eif_dense_shape(int D, int32_t max_nodes, int32_t max_internal,
+                             int* rpt, int* threads, size_t* lds);
+hipError_t launch_explain_extended_dense(
+    RowDtype dt, int D, const void* X, const void* nodes, const float* rows,
+    const int32_t* ncnt, const int32_t* icnt, float* out, int64_t N, int32_t d,
+    int64_t rs, int64_t cs, int32_t T, int32_t max_nodes, int32_t max_internal,
+    int32_t height, float fT, int finalize, size_t lds, int blocks,
+    hipStream_t stream);
+
 // bag_kernels.hip
 int launch_bag_sample_lds(int64_t* out, int32_t* err, uint64_t seed,
                           uint32_t tree0, int32_t T, uint32_t N, int32_t n,
@@ -2215,6 +2225,103 @@ torch::Tensor explain_extended_forest(torch::Tensor X,
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// Per-feature attribution, extended forests whose whole tree fits in LDS
+// (explain_extended_dense_kernel, explain_kernels.hip).
+// ---------------------------------------------------------------------------
+
+struct ExplainEifDenseCfg {
+  int D, rpt, threads, trees;
+  size_t lds;
+};
+
+// The instantiation rows of d columns run against trees of at most
+// max_internal internal nodes in arrays max_nodes wide, or zeros where the
+// kernel has none or one tree's stage does not fit in LDS.
+ExplainEifDenseCfg pick_explain_eif_dense_cfg(int64_t d, int64_t max_nodes,
+                                              int64_t max_internal) {
+  if (d < 1 || d > 32 || max_nodes < 1 || max_nodes > 32767)
+    return {0, 0, 0, 0, 0};
+  ExplainEifDenseCfg c{d <= 8 ? 8 : (d <= 16 ? 16 : 32), 0, 0, 1, 0};
+  ifa::explain_eif_dense_shape(c.D, (int32_t)max_nodes, (int32_t)max_internal,
+                               &c.rpt, &c.threads, &c.lds);
+  if (c.rpt == 0 || c.lds > kMaxLds) return {0, 0, 0, 0, 0};
+  return c;
+}
+
+// (D, rows per thread, trees per barrier phase, block threads) of the dense
+// EIF explain kernel for rows of this kind and width and node arrays
+// max_nodes wide (every tree taken at its fullest, (max_nodes - 1) / 2
+// internal nodes), or zeros where gpu_engine must keep the strict kernel.
+// A block's row tile is rows per thread times block threads.
+std::tuple<int64_t, int64_t, int64_t, int64_t> explain_eif_dense_cfg(
+    const std::string& dtype, int64_t d, int64_t max_nodes) {
+  (void)elem_bytes_of(dtype);  // rows live in registers: only checked
+  const ExplainEifDenseCfg c = pick_explain_eif_dense_cfg(
+      d, max_nodes, std::max<int64_t>((max_nodes - 1) / 2, 1));
+  return {c.D, c.rpt, c.trees, c.threads};
+}
+
+// `nodes` int32 [T, max_nodes, 2] and `rows` f32 [T, MI, 3, D] are the
+// ("eif_explain_dense", D) pack of gpu_engine; ncount / icount [T] count a
+// tree's live records and its internal nodes. Returns the f32 [N, d]
+// contribution matrix (raw sums when !finalize).
+torch::Tensor explain_extended_dense(torch::Tensor X, torch::Tensor nodes,
+                                     torch::Tensor rows, torch::Tensor ncount,
+                                     torch::Tensor icount, int64_t height,
+                                     bool finalize) {
+  CHECK_CUDA(X);
+  for (const torch::Tensor* a : {&nodes, &rows, &ncount, &icount}) {
+    CHECK_CUDA(*a);
+    CHECK_CONTIG(*a);
+  }
+  check_x(X);
+  const XLayout xl = check_x_layout(X);
+  TORCH_CHECK(nodes.dim() == 3 && nodes.size(2) == 2 &&
+                  nodes.scalar_type() == torch::kInt32,
+              "nodes must be int32 [T, max_nodes, 2]");
+  const int64_t N = X.size(0), d = X.size(1);
+  const int64_t T = nodes.size(0), max_nodes = nodes.size(1);
+  TORCH_CHECK(rows.dim() == 4 && rows.scalar_type() == torch::kFloat32 &&
+                  rows.size(0) == T && rows.size(2) == 3,
+              "rows must be float32 [T, MI, 3, D]");
+  const int64_t max_internal = rows.size(1), D = rows.size(3);
+  TORCH_CHECK(max_internal >= 1 && 2 * max_internal + 1 <= max_nodes + 2,
+              "more internal nodes than the node arrays hold");
+  for (const torch::Tensor* a : {&ncount, &icount})
+    TORCH_CHECK(a->scalar_type() == torch::kInt32 && a->dim() == 1 &&
+                    a->size(0) == T,
+                "ncount and icount must be int32 [T]");
+  TORCH_CHECK(T >= 1, "explain needs at least one tree");
+  TORCH_CHECK(height >= 0 && height <= 64, "height out of range");
+  const ExplainEifDenseCfg cfg =
+      pick_explain_eif_dense_cfg(d, max_nodes, max_internal);
+  TORCH_CHECK(cfg.D > 0 && cfg.D == D,
+              "no dense explain kernel for rows of ", d, " columns against a "
+              "pack of ", D, " columns and ", max_nodes, " node slots");
+  // every cell of a live row is written by the tile's flush
+  auto out = torch::empty({N, d}, X.options().dtype(torch::kFloat32));
+  if (N == 0) return out;
+  int64_t max_blocks = 8192;
+  if (const char* e = getenv("IFA_EXPLAIN_MAX_BLOCKS")) {
+    const int64_t v = atoll(e);
+    if (v >= 1) max_blocks = std::min<int64_t>(v, 8192);
+  }
+  const int64_t tile = (int64_t)cfg.rpt * cfg.threads;
+  const int blocks =
+      (int)std::min<int64_t>((N + tile - 1) / tile, max_blocks);
+  const hipError_t err = ifa::launch_explain_extended_dense(
+      row_dtype(X), cfg.D, X.data_ptr(), nodes.data_ptr<int32_t>(),
+      rows.data_ptr<float>(), ncount.data_ptr<int32_t>(),
+      icount.data_ptr<int32_t>(), out.data_ptr<float>(), N, (int32_t)d, xl.rs,
+      xl.cs, (int32_t)T, (int32_t)max_nodes, (int32_t)max_internal,
+      (int32_t)height, (float)T, finalize ? 1 : 0, cfg.lds, blocks,
+      current_stream());
+  TORCH_CHECK(err == hipSuccess, "explain_extended_dense launch failed (",
+              cfg.lds, " B of LDS): ", hipGetErrorString(err));
+  return out;
+}
+
 // Exact TreeSHAP, standard forests (shap_forest_kernel, docs/DESIGN.md §9).
 // `table` is the leaf-path word stream of gpu_engine._shap_packed for X's row
 // kind, `tree_off` its per-tree word offsets: once on the host (checked
@@ -2480,6 +2587,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-feature path-length attribution, standard forests");
   m.def("explain_extended_forest", &explain_extended_forest,
         "per-feature path-length attribution, extended forests");
+  m.def("explain_eif_dense_cfg", &explain_eif_dense_cfg,
+        "(D, rows per thread, trees per phase, block threads) of the dense "
+        "EIF explain kernel for (dtype, d, max_nodes); zeros: no route");
+  m.def("explain_extended_dense", &explain_extended_dense,
+        "EIF contributions, whole tree in LDS, rows and sums in registers");
   m.def("shap_forest", &shap_forest,
         "exact path-dependent TreeSHAP values, standard forests");
   m.def("shap_deep_cfg", &shap_deep_cfg,
