@@ -1372,6 +1372,27 @@ int64_t deep_stage(const std::string& dtype, int64_t d) {
   return pick_deep_cfg(elem_bytes_of(dtype), d).stage;
 }
 
+// (rows per thread, stage) of the instantiation these shapes run, or (0, 0)
+// where deep_stage is 0
+std::tuple<int64_t, int64_t> score_deep_cfg(const std::string& dtype,
+                                            int64_t d) {
+  if (d < 1 || d > 4094) return {0, 0};
+  const DeepCfg cfg = pick_deep_cfg(elem_bytes_of(dtype), d);
+  return {cfg.rpt, cfg.stage};
+}
+
+// The most blocks score_forest_deep and score_extended_deep launch; past it a
+// block strides over row tiles. IFA_SCORE_DEEP_MAX_BLOCKS=<n> lowers the
+// limit so that tests reach the stride at small N.
+int64_t score_deep_max_blocks() {
+  int64_t max_blocks = 8192;
+  if (const char* e = getenv("IFA_SCORE_DEEP_MAX_BLOCKS")) {
+    const int64_t v = atoll(e);
+    if (v >= 1) max_blocks = std::min<int64_t>(v, 8192);
+  }
+  return max_blocks;
+}
+
 // trimmed pre-order arrays [T, M0] (feature id or < 0 for a leaf, pre-order
 // right child, key threshold or leaf value bits) -> the deep records
 // int32 [Tpad, M, 2] and lds_levels int32 [Tpad] for a stage of `stage`
@@ -1450,7 +1471,7 @@ torch::Tensor score_forest_deep(torch::Tensor X, torch::Tensor records,
   if (N == 0) return out;
   const int64_t rows_per_block = (int64_t)cfg.rpt * 256;
   const int blocks = (int)std::min<int64_t>(
-      (N + rows_per_block - 1) / rows_per_block, 8192);
+      (N + rows_per_block - 1) / rows_per_block, score_deep_max_blocks());
   const hipError_t err = ifa::launch_score_forest_deep(
       dt, cfg.rpt, X.data_ptr(), records.data_ptr<int32_t>(),
       lds_levels.data_ptr<int32_t>(), out.data_ptr<float>(), N, (int32_t)d,
@@ -1522,6 +1543,15 @@ ExplainDeepCfg pick_explain_deep_cfg(int elem_bytes, int64_t d) {
 int64_t explain_deep_stage(const std::string& dtype, int64_t d) {
   if (d < 1 || d > 4094) return 0;
   return pick_explain_deep_cfg(elem_bytes_of(dtype), d).stage;
+}
+
+// (rows per thread, stage, accumulators in LDS) of the instantiation these
+// shapes run, or (0, 0, false) where explain_deep_stage is 0
+std::tuple<int64_t, int64_t, bool> explain_deep_cfg(const std::string& dtype,
+                                                    int64_t d) {
+  if (d < 1 || d > 4094) return {0, 0, false};
+  const ExplainDeepCfg cfg = pick_explain_deep_cfg(elem_bytes_of(dtype), d);
+  return {cfg.rpt, cfg.stage, cfg.acc_lds};
 }
 
 // trimmed pre-order arrays [T, M0] (deep_level_order's three, plus the f32
@@ -1692,6 +1722,17 @@ int64_t explain_eif_deep_stage(const std::string& dtype, int64_t d,
                                int64_t nnz) {
   if (d < 1 || d > 4094 || nnz < 1 || nnz > 4094) return 0;
   return pick_explain_eif_deep_cfg(elem_bytes_of(dtype), d, nnz).stage;
+}
+
+// (rows per thread, trees per barrier phase, stage, accumulators in LDS) of
+// the instantiation these shapes run, or zeros where explain_eif_deep_stage
+// is 0
+std::tuple<int64_t, int64_t, int64_t, bool> explain_eif_deep_cfg(
+    const std::string& dtype, int64_t d, int64_t nnz) {
+  if (d < 1 || d > 4094 || nnz < 1 || nnz > 4094) return {0, 0, 0, false};
+  const ExplainEifDeepCfg cfg =
+      pick_explain_eif_deep_cfg(elem_bytes_of(dtype), d, nnz);
+  return {cfg.rpt, cfg.trees, cfg.stage, cfg.acc_lds};
 }
 
 // Trimmed pre-order arrays of an extended forest -> the explain eif deep
@@ -2025,7 +2066,7 @@ torch::Tensor score_extended_deep(torch::Tensor X, torch::Tensor nodes,
   if (N == 0) return out;
   const int64_t rows_per_block = (int64_t)cfg.rpt * 256;
   const int blocks = (int)std::min<int64_t>(
-      (N + rows_per_block - 1) / rows_per_block, 8192);
+      (N + rows_per_block - 1) / rows_per_block, score_deep_max_blocks());
   const hipError_t err = ifa::launch_score_extended_deep(
       dt, cfg.rpt, cfg.phase, X.data_ptr(), nodes.data_ptr<int32_t>(),
       hyper.data_ptr<int32_t>(), lds_levels.data_ptr<int32_t>(),
@@ -2601,12 +2642,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "exact TreeSHAP past 15-bit node ids: G lanes a row, one entry a lane");
   m.def("deep_stage", &deep_stage,
         "records per tree score_forest_deep stages for (dtype, d); 0: none");
+  m.def("score_deep_cfg", &score_deep_cfg,
+        "(rows per thread, stage) score_forest_deep runs (dtype, d) with");
   m.def("deep_level_order", &deep_level_order,
         "trimmed pre-order arrays -> deep level-order records, lds_levels");
   m.def("score_forest_deep", &score_forest_deep,
         "standard forests past 15-bit node ids: LDS top levels, L2 tail");
   m.def("explain_deep_stage", &explain_deep_stage,
         "records per tree explain_forest_deep stages for (dtype, d); 0: none");
+  m.def("explain_deep_cfg", &explain_deep_cfg,
+        "(rows per thread, stage, accumulators in LDS) explain_forest_deep "
+        "runs (dtype, d) with");
   m.def("explain_deep_level_order", &explain_deep_level_order,
         "trimmed pre-order arrays and edge deltas -> explain deep records, "
         "lds_levels");
@@ -2615,6 +2661,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("explain_eif_deep_stage", &explain_eif_deep_stage,
         "records per tree explain_extended_deep stages for (dtype, d, nnz); "
         "0: none");
+  m.def("explain_eif_deep_cfg", &explain_eif_deep_cfg,
+        "(rows per thread, trees per phase, stage, accumulators in LDS) "
+        "explain_extended_deep runs (dtype, d, nnz) with");
   m.def("explain_eif_deep_pack", &explain_eif_deep_pack,
         "trimmed pre-order extended forest -> level-order node records, "
         "per-coordinate payload, lds_levels");
