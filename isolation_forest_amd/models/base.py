@@ -52,11 +52,83 @@ def extract_features(data, features_col: str) -> Tuple[torch.Tensor, object]:
     if isinstance(data, torch.Tensor):
         if data.dim() != 2:
             raise ValueError(f"expected 2-D feature matrix, got shape {tuple(data.shape)}")
+        is_csr(data)  # refuses the other sparse layouts
         return data, "torch"
+    if type(data).__module__.startswith("scipy.sparse"):
+        csr_unsupported("a scipy sparse matrix (sparse input is a "
+                        "torch.sparse_csr tensor)")
     raise TypeError(
         "fit/transform accept numpy.ndarray [N,d], torch.Tensor [N,d] or a "
         f"pandas DataFrame with a features column; got {type(data).__name__}"
     )
+
+
+# -- sparse CSR input (docs/API.md "Sparse input") --------------------------
+
+# Dense float32 bytes the CPU paths hold of a sparse matrix at a time.
+CSR_CHUNK_BYTES = 64 << 20
+
+
+def is_csr(X) -> bool:
+    """True for a ``torch.sparse_csr`` tensor; any other sparse layout is
+    refused here, so callers branch on dense or CSR only."""
+    if not isinstance(X, torch.Tensor) or X.layout == torch.strided:
+        return False
+    if X.layout != torch.sparse_csr:
+        csr_unsupported(f"a {X.layout} tensor (sparse input is "
+                        "torch.sparse_csr only)")
+    return True
+
+
+def csr_unsupported(what: str):
+    raise NotImplementedError(
+        f"{what} is not supported: densify the rows first (X.to_dense(); "
+        "docs/API.md, Sparse input)")
+
+
+def _csr_host_parts(X: torch.Tensor):
+    """Validated parts of a CPU CSR matrix as numpy: (crow int64, col,
+    values float32 — widened exactly —, N, d)."""
+    from ..ops import gpu_engine
+
+    crow, col, values, N, d = gpu_engine._csr_parts(X)
+    return (crow.to(torch.int64).numpy(), col.numpy(),
+            values.float().numpy(), N, d)
+
+
+def _csr_dense_rows(parts, rows: np.ndarray) -> np.ndarray:
+    """Rows ``rows`` of the matrix as dense float32 [len(rows), d]: what
+    ``X.to_dense()[rows]`` holds, an absent cell +0.0."""
+    crow, col, values, _, d = parts
+    lo = crow[rows]
+    ln = crow[rows + 1] - lo
+    out = np.zeros((len(rows), d), dtype=np.float32)
+    total = int(ln.sum())
+    if total:
+        rep = np.repeat(np.arange(len(rows)), ln)
+        ent = (np.arange(total) - np.repeat(np.cumsum(ln) - ln, ln)
+               + np.repeat(lo, ln))
+        out[rep, col[ent]] = values[ent]
+    return out
+
+
+def csr_dense_chunks(X: torch.Tensor):
+    """A CPU CSR matrix as dense float32 row chunks of at most
+    ``CSR_CHUNK_BYTES`` (at least one row; one empty chunk for N = 0)."""
+    parts = _csr_host_parts(X)
+    N, d = parts[3], parts[4]
+    step = max(1, CSR_CHUNK_BYTES // (4 * d))
+    for r0 in range(0, max(N, 1), step):
+        yield _csr_dense_rows(parts, np.arange(r0, min(N, r0 + step)))
+
+
+def csr_bag_rows(X: torch.Tensor, bag_idx: np.ndarray):
+    """``(Xu, bags)`` for the CPU builders: the distinct bag rows of a CPU
+    CSR matrix as dense float32, and ``bag_idx`` renumbered into them, so
+    that ``Xu[bags[t]]`` is ``X.to_dense()[bag_idx[t]]``."""
+    uniq, inv = np.unique(bag_idx, return_inverse=True)
+    return (_csr_dense_rows(_csr_host_parts(X), uniq),
+            inv.reshape(bag_idx.shape).astype(np.int64))
 
 
 def check_output_columns(data, kind, score_col: str, prediction_col: str):
@@ -151,6 +223,8 @@ class ModelBase:
             raise ValueError(
                 f"unknown attribution method {method!r}: expected one of "
                 f"{self.EXPLAIN_METHODS}")
+        if is_csr(X):
+            csr_unsupported("feature attribution of a sparse CSR matrix")
         self._check_scorable()
         validate_feature_vector_size(self.forest.total_num_features, X.shape[1])
         if method == "shap":

@@ -26,6 +26,9 @@ class ExtendedIsolationForest(IsolationForest):
         return ExtendedIsolationForestModel
 
     def _build_local(self, X, rp, seed, t_lo, t_hi, n_local):
+        if base.is_csr(X):
+            base.csr_unsupported(
+                "ExtendedIsolationForest on a sparse CSR matrix")
         T_local = t_hi - t_lo
         feat_sub = cpu_engine.feature_subsets(
             rp.total_features, rp.num_features, T_local, seed, tree_id_offset=t_lo
@@ -124,6 +127,9 @@ class ExtendedIsolationForestModel(ModelBase):
             )
 
     def score(self, X: torch.Tensor) -> torch.Tensor:
+        if base.is_csr(X):
+            base.csr_unsupported(
+                "ExtendedIsolationForest on a sparse CSR matrix")
         self._check_scorable()
         base.validate_feature_vector_size(self.forest.total_num_features, X.shape[1])
         if isinstance(X, torch.Tensor) and X.is_cuda:

@@ -148,6 +148,9 @@ class IsolationForest:
         feat_sub = cpu_engine.feature_subsets(
             rp.total_features, rp.num_features, T_local, seed, tree_id_offset=t_lo
         )
+        csr = base.is_csr(X)
+        if csr and rp.num_samples > 16384:
+            base.csr_unsupported("maxSamples > 16384 on a sparse CSR matrix")
         if X.is_cuda:
             from ..ops import gpu_engine
 
@@ -168,7 +171,10 @@ class IsolationForest:
             )
             X = X.float().cpu()
         bag_idx = self._host_bags(rp, seed, t_lo, t_hi, n_local)
-        Xc = X.contiguous().float().numpy()
+        if csr:  # only the bags' rows are densified
+            Xc, bag_idx = base.csr_bag_rows(X, bag_idx)
+        else:
+            Xc = X.contiguous().float().numpy()
         return cpu_engine.build_forest(
             Xc, bag_idx, feat_sub, seed, rp.num_samples, rp.num_features,
             rp.total_features, tree_id_offset=t_lo,
@@ -273,12 +279,32 @@ class IsolationForestModel(ModelBase):
         """Outlier scores, float32 tensor on X's device."""
         self._check_scorable()
         base.validate_feature_vector_size(self.forest.total_num_features, X.shape[1])
+        if base.is_csr(X):
+            return self._score_csr(X)
         if isinstance(X, torch.Tensor) and X.is_cuda:
             from ..ops import gpu_engine
 
             return gpu_engine.score_forest(self, X)
         Xc = X.contiguous().float().numpy() if isinstance(X, torch.Tensor) else X
         return torch.from_numpy(cpu_engine.score_forest(self.forest, Xc))
+
+    def _score_csr(self, X: torch.Tensor) -> torch.Tensor:
+        """``score`` of a ``torch.sparse_csr`` matrix, bitwise the dense
+        call on ``X.to_dense()``: the CSR kernel on the device, the CPU
+        engine over dense row chunks of bounded size on the host."""
+        import numpy as np
+
+        from ..ops import gpu_engine
+
+        if not gpu_engine._packed_fits(self.forest, int(X.shape[1])):
+            base.csr_unsupported(
+                "a forest past maxSamples 16384 or 4094 features on a "
+                "sparse CSR matrix")
+        if X.is_cuda:
+            return gpu_engine.score_forest_csr(self, X)
+        return torch.from_numpy(np.concatenate(
+            [cpu_engine.score_forest(self.forest, Xc)
+             for Xc in base.csr_dense_chunks(X)]))
 
     def transform(self, data, comm=None):
         """Append score + predicted-label columns

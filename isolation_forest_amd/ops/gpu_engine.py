@@ -33,6 +33,12 @@ Standard forests past the 15-bit node ids (maxSamples > 16384) score through
 compact level-order records, top levels in LDS and the tail from L2
 (score_forest_deep; large_score_route), and fall back to the wide kernel
 past that format's own caps.
+
+``torch.sparse_csr`` matrices (standard forests inside the packed caps) are
+scored without a dense copy by the tree-parallel walk of
+ops/hip/csr_kernels.hip (score_forest_csr) over the same v4 pack, and built
+from bags scattered out of the stored entries (build_forest); both bitwise
+the dense calls on ``X.to_dense()``.
 """
 
 from __future__ import annotations
@@ -84,6 +90,68 @@ def _rows_in_place(X: torch.Tensor) -> torch.Tensor:
                "making one contiguous copy", tuple(X.stride()),
                tuple(X.shape))
     return X.contiguous()
+
+
+_CSR_DENSIFY = ("{} is not supported: densify the rows first (X.to_dense(); "
+                "docs/API.md, Sparse input)")
+
+
+def _first_true(mask: torch.Tensor) -> torch.Tensor:
+    """0-d int64 tensor: index of the first True, or ``mask.numel()``."""
+    n = mask.numel()
+    if n == 0:
+        return torch.zeros((), dtype=torch.int64, device=mask.device)
+    return torch.where(mask.any(), mask.to(torch.uint8).argmax(),
+                       torch.full((), n, dtype=torch.int64,
+                                  device=mask.device))
+
+
+def _csr_parts(X: torch.Tensor):
+    """``(crow_indices, col_indices, values, N, d)`` of a 2-D
+    ``torch.sparse_csr`` matrix, validated with torch ops on X's device and
+    one host sync: ``crow`` non-decreasing from 0 to nnz, every column in
+    ``[0, d)``, columns strictly ascending within a row. A duplicated or
+    unsorted column has no agreed dense meaning, so it is refused with a
+    ``ValueError`` that names the first offending row. The only temporaries
+    are masks of one byte per stored entry and an int64 copy of ``crow``."""
+    if X.layout != torch.sparse_csr or X.dim() != 2:
+        raise ValueError("expected a 2-D torch.sparse_csr matrix, got "
+                         f"layout {X.layout} with {X.dim()} dimensions")
+    crow, col, values = X.crow_indices(), X.col_indices(), X.values()
+    N, d = int(X.shape[0]), int(X.shape[1])
+    _row_kind(values.dtype)
+    if values.dim() != 1 or d < 1:
+        raise ValueError("a sparse CSR matrix needs scalar values and at "
+                         f"least one column; got values of shape "
+                         f"{tuple(values.shape)} and d = {d}")
+    nnz = int(values.shape[0])
+    c64 = crow.to(torch.int64)
+    bad_row = (c64[:-1] < 0) | (c64[1:] < c64[:-1]) | (c64[1:] > nnz)
+    ends_ok = (c64[0] == 0) & (c64[-1] == nnz)
+    cc = c64.clamp(0, nnz)  # safe to index with, whatever crow holds
+    bad_col = (col < 0) | (col >= d)
+    starts = torch.zeros(nnz + 1, dtype=torch.bool, device=col.device)
+    starts[cc[:-1]] = True
+    bad_ord = (col[1:] <= col[:-1]) & ~starts[1:nnz]
+    e_col, e_ord = _first_true(bad_col), _first_true(bad_ord) + 1
+    entries = torch.stack([e_col, e_ord])
+    rows = torch.searchsorted(cc, entries, right=True) - 1
+    r_crow, ok, e_col, e_ord, r_col, r_ord = torch.cat([
+        torch.stack([_first_true(bad_row), ends_ok.to(torch.int64)]),
+        entries, rows]).tolist()
+    if r_crow < N or not ok:
+        row = r_crow if r_crow < N else (0 if int(c64[0]) != 0 else N - 1)
+        raise ValueError(
+            f"sparse CSR input: crow_indices must be non-decreasing from 0 "
+            f"to nnz = {nnz}; first offending row {row}")
+    if e_col < nnz:
+        raise ValueError(
+            f"sparse CSR input: column index outside [0, {d}) in row {r_col}")
+    if e_ord < nnz:
+        raise ValueError(
+            "sparse CSR input: column indices must be strictly ascending "
+            f"within a row (no duplicates); first offending row {r_ord}")
+    return crow.contiguous(), col.contiguous(), values.contiguous(), N, d
 
 
 def _leaf_lut(n: int, device) -> torch.Tensor:
@@ -219,7 +287,15 @@ def build_forest(X: torch.Tensor, bag_idx, feat_sub: np.ndarray,
     max_nodes = 2 * n - 1
     bag_t = _bag_tensor(bag_idx, device)
     fs_t = torch.from_numpy(np.ascontiguousarray(feat_sub, dtype=np.int32)).to(device)
-    bags = ext.bag_gather(_rows_in_place(X), bag_t)
+    if X.layout == torch.sparse_csr:
+        # the same f32 [T, n, d] bags, scattered from the stored entries
+        if n > 16384:
+            raise NotImplementedError(_CSR_DENSIFY.format(
+                "maxSamples > 16384 on a sparse CSR matrix"))
+        crow, col, values, _, d = _csr_parts(X)
+        bags = ext.bag_gather_csr(crow, col, values, d, bag_t)
+    else:
+        bags = ext.bag_gather(_rows_in_place(X), bag_t)
     feat, value, right, count, ncount, depth = ext.build_forest(
         bags, fs_t, seed, tree_id_offset, _leaf_lut(n, device), max_nodes,
         height_limit,
@@ -1887,6 +1963,31 @@ def score_forest(model, X: torch.Tensor, finalize: bool = True) -> torch.Tensor:
     return ext.score_forest(
         _rows_in_place(X), aos, ncount, forest.num_trees, extra["height"], c,
         finalize, _heap_for_call(aos, extra, d, kind),
+    )
+
+
+def score_forest_csr(model, X: torch.Tensor,
+                     finalize: bool = True) -> torch.Tensor:
+    """``score_forest`` for a ``torch.sparse_csr`` matrix on the device,
+    bitwise the dense call on ``X.to_dense()``: an absent cell is +0.0, and
+    no dense copy is made (ops/hip/csr_kernels.hip walks the (d, kind) pack
+    of the dense route). Standard forests inside the packed caps only."""
+    ext = load_extension()
+    forest = model.forest
+    if isinstance(forest, ExtendedForest):
+        raise NotImplementedError(_CSR_DENSIFY.format(
+            "an extended forest on a sparse CSR matrix"))
+    crow, col, values, N, d = _csr_parts(X)
+    kind = _row_kind(values.dtype)
+    if not _packed_fits(forest, d):
+        raise NotImplementedError(_CSR_DENSIFY.format(
+            "a forest past maxSamples 16384 or 4094 features on a sparse "
+            "CSR matrix"))
+    c = float(avg_path_length(forest.num_samples))
+    aos, ncount, extra = _device_forest(model, X.device, v4_key=(d, kind))
+    return ext.score_forest_csr(
+        crow, col, values, N, d, aos, ncount.contiguous(), forest.num_trees,
+        extra["height"], c, finalize,
     )
 
 

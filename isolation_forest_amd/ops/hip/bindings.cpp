@@ -276,6 +276,20 @@ void launch_bag_bootstrap(int64_t* out, uint64_t seed, uint32_t tree0,
 void launch_bag_dense_keys(int64_t* keys, uint64_t seed, uint32_t tree0,
                            int64_t T, int64_t N, hipStream_t stream);
 
+// csr_kernels.hip
+hipError_t launch_score_forest_csr(
+    RowDtype dt, bool idx64, int G, bool nodes_lds, const void* crow,
+    const void* col, const void* values, int64_t nnz, const void* nodes,
+    const int32_t* ncnt, float* out, int64_t N, int32_t d, int32_t SW,
+    int32_t Tpad, int32_t max_nodes, int32_t height, int32_t PH, float fT,
+    float c_norm, int finalize, size_t lds, int blocks, hipStream_t stream);
+hipError_t launch_bag_gather_csr(RowDtype dt, bool idx64, const void* crow,
+                                 const void* col, const void* values,
+                                 int64_t nnz, int64_t N,
+                                 const int64_t* bag_idx, float* bags,
+                                 int64_t TN, int64_t d, int blocks,
+                                 hipStream_t stream);
+
 }  // namespace ifa
 
 namespace {
@@ -2560,6 +2574,186 @@ torch::Tensor shap_forest_deep(torch::Tensor X, torch::Tensor table,
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// sparse CSR input (csr_kernels.hip, docs/DESIGN.md §3c)
+// ---------------------------------------------------------------------------
+
+namespace {
+
+// The instantiation one CSR scoring call runs, from shapes alone. A block of
+// 256 threads holds the full key vectors of R rows, row-major with a stride
+// of SW 32-bit words: at least the words of d + 1 keys, and odd, so that
+// consecutive rows start in different banks. G = 256 / R lanes share a row's
+// trees; a barrier phase is PH = m * G trees, m <= 4 chains a lane.
+//
+// Records in LDS (the v4 walk's preference): the tile takes the largest R
+// within HALF the 150 KB budget, and the rest, less the 4 KB of leaf-value
+// slots, must stage at least one tree per lane of a group (m >= 1). Where it
+// does not, the records are read from global memory / L2, the tile takes the
+// largest R that fits the budget alone, and m = 4.
+struct CsrCfg {
+  int R, G, PH, SW;
+  bool nodes_lds;
+  size_t lds;
+};
+
+constexpr size_t kCsrBudget = 150 * 1024;
+constexpr size_t kCsrSlots = 4 * 256 * sizeof(float);
+
+CsrCfg pick_csr_cfg(int elem_bytes, int64_t d, int64_t max_nodes) {
+  CsrCfg c{};
+  c.SW = (int)(elem_bytes == 4 ? (d + 1) | 1 : ((d + 2) / 2) | 1);
+  const size_t row_bytes = (size_t)c.SW * 4;
+  auto rows_within = [&](size_t share) {
+    int R = 256;
+    while (R > 4 && (size_t)R * row_bytes > share) R >>= 1;
+    return R;
+  };
+  const size_t tree = (size_t)max_nodes * 8;
+  c.R = rows_within(kCsrBudget / 2);
+  c.G = 256 / c.R;
+  size_t tile = (size_t)c.R * row_bytes;
+  const size_t fit = (kCsrBudget - kCsrSlots - tile) / tree;
+  const int m = (int)std::min<size_t>(fit / (size_t)c.G, 4);
+  if (m >= 1) {
+    c.nodes_lds = true;
+    c.PH = m * c.G;
+    c.lds = (size_t)c.PH * tree + kCsrSlots + tile;
+    return c;
+  }
+  c.nodes_lds = false;
+  c.R = rows_within(kCsrBudget - kCsrSlots);
+  c.G = 256 / c.R;
+  tile = (size_t)c.R * row_bytes;
+  c.PH = 4 * c.G;
+  c.lds = kCsrSlots + tile;
+  return c;
+}
+
+struct CsrParts {
+  ifa::RowDtype dt;
+  bool idx64;
+  int64_t nnz;
+};
+
+// crow [N + 1], col [nnz] (both int32 or both int64) and values [nnz] of a
+// CSR matrix with N rows, contiguous on one device
+CsrParts check_csr(const torch::Tensor& crow, const torch::Tensor& col,
+                   const torch::Tensor& values, int64_t N, int64_t d) {
+  CHECK_CUDA(crow);
+  CHECK_CUDA(col);
+  CHECK_CUDA(values);
+  CHECK_CONTIG(crow);
+  CHECK_CONTIG(col);
+  CHECK_CONTIG(values);
+  TORCH_CHECK(N >= 0 && d >= 1, "a CSR matrix needs N >= 0 and d >= 1");
+  TORCH_CHECK(crow.dim() == 1 && crow.size(0) == N + 1,
+              "crow_indices must be [N + 1]");
+  TORCH_CHECK(col.dim() == 1 && values.dim() == 1 &&
+                  col.size(0) == values.size(0),
+              "col_indices and values must be [nnz]");
+  TORCH_CHECK((crow.scalar_type() == torch::kInt32 ||
+               crow.scalar_type() == torch::kInt64) &&
+                  col.scalar_type() == crow.scalar_type(),
+              "crow_indices and col_indices must both be int32 or int64");
+  TORCH_CHECK(values.scalar_type() == torch::kFloat32 ||
+                  values.scalar_type() == torch::kBFloat16 ||
+                  values.scalar_type() == torch::kHalf,
+              "values must be float32, bfloat16 or float16");
+  TORCH_CHECK(col.device() == crow.device() &&
+                  values.device() == crow.device(),
+              "the parts of a CSR matrix must share a device");
+  return {row_dtype(values), crow.scalar_type() == torch::kInt64,
+          values.size(0)};
+}
+
+}  // namespace
+
+// (rows per block R, lanes per row G, trees per barrier phase PH, records in
+// LDS) of the CSR scoring walk for these shapes; `height` does not move it
+std::tuple<int64_t, int64_t, int64_t, bool> score_csr_cfg(
+    const std::string& dtype, int64_t d, int64_t max_nodes, int64_t height) {
+  TORCH_CHECK(dtype == "bf16" || dtype == "f16" || dtype == "f32",
+              "dtype must be bf16, f16 or f32");
+  TORCH_CHECK(d >= 1 && d <= 4094 && max_nodes >= 1 && max_nodes <= 32767,
+              "CSR scoring takes 1 <= d <= 4094 and 15-bit node ids");
+  (void)height;
+  const CsrCfg c = pick_csr_cfg(dtype == "f32" ? 4 : 2, d, max_nodes);
+  return {c.R, c.G, c.PH, c.nodes_lds};
+}
+
+torch::Tensor score_forest_csr(torch::Tensor crow, torch::Tensor col,
+                               torch::Tensor values, int64_t N, int64_t d,
+                               torch::Tensor nodes_packed,
+                               torch::Tensor ncount, int64_t num_trees,
+                               int64_t height_limit, double c_norm,
+                               bool finalize) {
+  const CsrParts cp = check_csr(crow, col, values, N, d);
+  CHECK_CUDA(nodes_packed);
+  CHECK_CONTIG(nodes_packed);
+  CHECK_CUDA(ncount);
+  CHECK_CONTIG(ncount);
+  TORCH_CHECK(nodes_packed.dim() == 3 && nodes_packed.size(2) == 2 &&
+                  nodes_packed.scalar_type() == torch::kInt32,
+              "nodes must be packed int32 [Tpad, max_nodes, 2]");
+  const int64_t Tpad = nodes_packed.size(0), max_nodes = nodes_packed.size(1);
+  TORCH_CHECK(ncount.scalar_type() == torch::kInt32 && ncount.dim() == 1 &&
+                  ncount.size(0) == Tpad,
+              "ncount must be int32 [Tpad]");
+  TORCH_CHECK(Tpad >= 1 && max_nodes >= 1 && max_nodes <= 32767,
+              "packed node ids are 15 bits");
+  TORCH_CHECK(d <= 4094, "scoring supports d <= 4094 (12-bit feature field "
+                         "plus the leaf sentinel column)");
+  TORCH_CHECK(height_limit >= 0 && height_limit <= 64, "bad height");
+  auto out = torch::empty({N}, values.options().dtype(torch::kFloat32));
+  if (N == 0) return out;
+
+  const CsrCfg cfg = pick_csr_cfg(ifa::row_elem_bytes(cp.dt), d, max_nodes);
+  // IFA_CSR_MAX_BLOCKS=<n> lowers the grid limit so that tests reach the
+  // grid-stride loop at small N
+  int64_t max_blocks = 8192;
+  if (const char* e = getenv("IFA_CSR_MAX_BLOCKS")) {
+    const int64_t v = atoll(e);
+    if (v >= 1) max_blocks = std::min<int64_t>(v, 8192);
+  }
+  const int blocks =
+      (int)std::min<int64_t>((N + cfg.R - 1) / cfg.R, max_blocks);
+  const hipError_t err = ifa::launch_score_forest_csr(
+      cp.dt, cp.idx64, cfg.G, cfg.nodes_lds, crow.data_ptr(), col.data_ptr(),
+      values.data_ptr(), cp.nnz, nodes_packed.data_ptr<int32_t>(),
+      ncount.data_ptr<int32_t>(), out.data_ptr<float>(), N, (int32_t)d,
+      (int32_t)cfg.SW, (int32_t)Tpad, (int32_t)max_nodes,
+      (int32_t)height_limit, (int32_t)cfg.PH, (float)num_trees, (float)c_norm,
+      finalize ? 1 : 0, cfg.lds, blocks, current_stream());
+  TORCH_CHECK(err == hipSuccess, "score_forest_csr launch failed (G = ",
+              cfg.G, ", ", cfg.lds, " B of LDS): ", hipGetErrorString(err));
+  return out;
+}
+
+// bag_gather for a CSR matrix: the same f32 [T, n, d] tensor, zero where the
+// row stores nothing
+torch::Tensor bag_gather_csr(torch::Tensor crow, torch::Tensor col,
+                             torch::Tensor values, int64_t d,
+                             torch::Tensor bag_idx) {
+  const int64_t N = crow.dim() == 1 ? crow.size(0) - 1 : -1;
+  const CsrParts cp = check_csr(crow, col, values, N, d);
+  CHECK_CUDA(bag_idx);
+  CHECK_CONTIG(bag_idx);
+  TORCH_CHECK(bag_idx.dim() == 2 && bag_idx.scalar_type() == torch::kInt64,
+              "bag_idx must be int64 [T, n]");
+  const int64_t T = bag_idx.size(0), n = bag_idx.size(1);
+  auto bags = torch::zeros({T, n, d}, values.options().dtype(torch::kFloat32));
+  if (T * n == 0) return bags;
+  const int blocks = (int)std::min<int64_t>((T * n + 3) / 4, 65536);
+  const hipError_t err = ifa::launch_bag_gather_csr(
+      cp.dt, cp.idx64, crow.data_ptr(), col.data_ptr(), values.data_ptr(),
+      cp.nnz, N, bag_idx.data_ptr<int64_t>(), bags.data_ptr<float>(), T * n, d,
+      blocks, current_stream());
+  TORCH_CHECK(err == hipSuccess, "bag_gather_csr launch failed: ",
+              hipGetErrorString(err));
+  return bags;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bag_gather", &bag_gather, "gather per-tree bags (K9/K10)");
   m.def("bag_sample_lds", &bag_sample_lds,
@@ -2684,5 +2878,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lds_levels"), py::arg("num_trees"), py::arg("height"),
         py::arg("stage"), py::arg("c"), py::arg("finalize"),
         py::arg("nnz") = 0);
+  m.def("score_csr_cfg", &score_csr_cfg,
+        "(rows per block R, lanes per row G, trees per phase PH, records in "
+        "LDS) of score_forest_csr for (dtype, d, max_nodes, height)",
+        py::arg("dtype"), py::arg("d"), py::arg("max_nodes"),
+        py::arg("height"));
+  m.def("score_forest_csr", &score_forest_csr,
+        "standard scoring of a CSR matrix: R rows' keys in LDS, trees shared "
+        "out among the lanes of a row",
+        py::arg("crow"), py::arg("col"), py::arg("values"), py::arg("N"),
+        py::arg("d"), py::arg("nodes_packed"), py::arg("ncount"),
+        py::arg("num_trees"), py::arg("height_limit"), py::arg("c_norm"),
+        py::arg("finalize"));
+  m.def("bag_gather_csr", &bag_gather_csr,
+        "gather per-tree bags from a CSR matrix", py::arg("crow"),
+        py::arg("col"), py::arg("values"), py::arg("d"), py::arg("bag_idx"));
   m.attr("WAVE") = 64;
 }
