@@ -2065,6 +2065,7 @@ def score_extended_forest(model, X: torch.Tensor, finalize: bool = True) -> torc
         return ext.score_forest(
             _rows_in_place(X), aos, ncount, forest.num_trees, extra["height"],
             c, finalize, _heap_for_call(aos, extra, d, X.dtype),
+            rowtile=False,  # extended forests keep the v4 / heap walks
         )
     if nnz <= 5 and _eif_uniform_nnz(forest):
         elem = 4 if X.dtype == torch.float32 else 2  # bf16 / fp16

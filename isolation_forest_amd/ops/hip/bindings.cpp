@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <string>
@@ -290,6 +291,14 @@ hipError_t launch_bag_gather_csr(RowDtype dt, bool idx64, const void* crow,
                                  int64_t TN, int64_t d, int blocks,
                                  hipStream_t stream);
 
+// rowtile_kernels.hip
+hipError_t launch_score_forest_rowtile(
+    RowDtype dt, int G, bool nodes_lds, const void* X, int64_t rs, int64_t cs,
+    const void* nodes, const int32_t* ncnt, float* out, int64_t N, int32_t d,
+    int32_t SW, int32_t Tpad, int32_t max_nodes, int32_t height, int32_t PH,
+    float fT, float c_norm, int finalize, size_t lds, int blocks,
+    hipStream_t stream);
+
 }  // namespace ifa
 
 namespace {
@@ -350,6 +359,48 @@ XLayout check_x_layout(const torch::Tensor& X) {
   return {1, s1};
 }
 
+// The instantiation score_forest_rowtile_kernel runs (rowtile_kernels.hip,
+// docs/DESIGN.md §3d), from shapes alone. A block of 256 threads holds the
+// full key vectors of R rows, row-major with a stride of SW 32-bit words: at
+// least the words of d + 1 keys, and odd. G = 256 / R lanes share a row's
+// trees; a barrier phase is PH = m * G trees, m <= 4 chains a lane.
+//
+// The tile takes the largest R within HALF the 150 KB budget, which with the
+// 4 KB of leaf-value slots keeps two blocks on a CU, and the records are read
+// in place from global memory / L2 with m = 4. Staging them in LDS instead
+// (csr_kernels.hip's preference) takes the rest of the budget, leaves one
+// block a CU and lost at every width and tree size measured, at m = 4 too;
+// so did a tile of the whole budget (profiles/score_rowtile.md).
+// IFA_ROWTILE_RECORDS=lds stages the records all the same, where at least one
+// tree per lane of a group fits beside the tile (m = min(fit / G, 4)), for
+// A/B runs and tests.
+struct RowtileCfg {
+  int R, G, PH, SW;
+  bool nodes_lds;
+  size_t lds;
+};
+
+constexpr size_t kRowtileBudget = 150 * 1024;
+constexpr size_t kRowtileSlots = 4 * 256 * sizeof(float);
+
+RowtileCfg pick_rowtile_cfg(int elem_bytes, int64_t d, int64_t max_nodes) {
+  RowtileCfg c{};
+  c.SW = (int)(elem_bytes == 4 ? (d + 1) | 1 : ((d + 2) / 2) | 1);
+  const size_t row_bytes = (size_t)c.SW * 4;
+  c.R = 256;
+  while (c.R > 4 && (size_t)c.R * row_bytes > kRowtileBudget / 2) c.R >>= 1;
+  c.G = 256 / c.R;
+  const size_t tile = (size_t)c.R * row_bytes;
+  const size_t tree = (size_t)max_nodes * 8;
+  const char* e = getenv("IFA_ROWTILE_RECORDS");
+  const size_t fit = (kRowtileBudget - kRowtileSlots - tile) / tree;
+  const int m = (int)std::min<size_t>(fit / (size_t)c.G, 4);
+  c.nodes_lds = e && !strcmp(e, "lds") && m >= 1;
+  c.PH = (c.nodes_lds ? m : 4) * c.G;
+  c.lds = (c.nodes_lds ? (size_t)c.PH * tree : 0) + kRowtileSlots + tile;
+  return c;
+}
+
 // The instantiation one standard scoring call runs, from shapes alone (and
 // the IFA_SCORE_* switches). score_forest launches by it, v4_heap_order lays
 // the heap records out for it, and score_route reports it.
@@ -358,6 +409,9 @@ struct ScoreCfg {
   int rpt, ilp;
   bool rows_lds, nodes_lds;
   size_t lds;
+  // score_forest_rowtile_kernel instead of either (pick_rowtile_cfg): the
+  // key tile does not fit at one row a thread, or IFA_SCORE_ROWTILE=1
+  bool rowtile;
   // score_forest_heap: taken when `heap` and the caller has the records
   // heap_rpt is tile rows / 256 (what the records' slab offsets are laid
   // out for); heap_threads (256 or 512) share the tile's rows out
@@ -451,15 +505,29 @@ ScoreCfg pick_score_cfg(int elem_bytes, int64_t d, int64_t max_nodes,
       lds = nodes_lds ? (size_t)ilp * max_nodes * 8 : 0;
     }
   }
+  // rows past the tile for a reason of shape go to the tree-parallel walk
+  // (profiles/score_rowtile.md). IFA_SCORE_FORCE_GLOBAL keeps meaning "the
+  // v4 walk with rows from global memory"; IFA_SCORE_ROWTILE=0 keeps that
+  // walk too, and =1 takes the new one for any shape, over heap and v4.
+  // Narrower rows, where the tile still fits beside records pushed out to
+  // L2 (16-bit d = 284 .. 299 at maxSamples 256), stay on v4: it won there.
+  bool rowtile = !rows_lds;
   bool force_global = false;
   if (const char* e = getenv("IFA_SCORE_FORCE_GLOBAL")) {
     if (atoi(e)) {
       force_global = true;
+      rowtile = false;
       rows_lds = false;
       rpt = 1;
       lds = nodes_lds ? (size_t)ilp * max_nodes * 8 : 0;
     }
   }
+  if (const char* e = getenv("IFA_SCORE_ROWTILE")) {
+    if (!strcmp(e, "0")) rowtile = false;
+    else if (!strcmp(e, "1")) rowtile = true;
+  }
+  c.rowtile = rowtile && max_nodes >= 1 && max_nodes <= 32767 && d >= 1 &&
+              d <= 4094;
   c.rpt = rpt;
   c.ilp = ilp;
   c.rows_lds = rows_lds;
@@ -491,8 +559,8 @@ ScoreCfg pick_score_cfg(int elem_bytes, int64_t d, int64_t max_nodes,
     const int v = atoi(e);
     if (v == 4 || v == 8) phase_want = v;
   }
-  if (heap_on && elem == 2 && rows_lds && nodes_lds && !force_global &&
-      !ilp_forced && height >= 1 && height <= 13) {
+  if (heap_on && !c.rowtile && elem == 2 && rows_lds && nodes_lds &&
+      !force_global && !ilp_forced && height >= 1 && height <= 13) {
     const size_t slots = (size_t)2 << height;
     struct HeapCand { int blocks, rpt; size_t lds; };
     auto best_of = [&](int phase) {
@@ -968,7 +1036,9 @@ torch::Tensor v4_heap_order(torch::Tensor nodes_packed, torch::Tensor ncount,
 }
 
 // which kernel family score_forest runs for these shapes: "heap", "v4",
-// "v4_global_nodes" (nodes walked from L2) or "v4_global_rows" (rows too).
+// "v4_global_nodes" (nodes walked from L2), "rowtile" (rows past the v4 key
+// tile, on the tree-parallel walk) or "v4_global_rows" (rows and nodes from
+// global memory).
 // `layout` ("packed", "pitched", "feature_major") picks an entry point of
 // the same family, never another route.
 std::string score_route(const std::string& dtype, int64_t d,
@@ -981,6 +1051,7 @@ std::string score_route(const std::string& dtype, int64_t d,
               "layout must be packed, pitched or feature_major");
   const ScoreCfg cfg =
       pick_score_cfg(dtype == "f32" ? 4 : 2, d, max_nodes, height);
+  if (cfg.rowtile) return "rowtile";
   if (cfg.heap) return "heap";
   if (!cfg.rows_lds) return "v4_global_rows";
   return cfg.nodes_lds ? "v4" : "v4_global_nodes";
@@ -999,6 +1070,20 @@ std::pair<int64_t, int64_t> score_heap_cfg(const std::string& dtype,
   return {cfg.heap_phase, cfg.heap_rpt};
 }
 
+// (rows per block R, lanes per row G, trees per barrier phase PH, records in
+// LDS) of score_forest_rowtile_kernel for these shapes, whether or not
+// score_route sends them there; `height` does not move it
+std::tuple<int64_t, int64_t, int64_t, bool> score_rowtile_cfg(
+    const std::string& dtype, int64_t d, int64_t max_nodes, int64_t height) {
+  TORCH_CHECK(dtype == "bf16" || dtype == "f16" || dtype == "f32",
+              "dtype must be bf16, f16 or f32");
+  TORCH_CHECK(d >= 1 && d <= 4094 && max_nodes >= 1 && max_nodes <= 32767,
+              "the rowtile walk takes 1 <= d <= 4094 and 15-bit node ids");
+  (void)height;
+  const RowtileCfg c = pick_rowtile_cfg(dtype == "f32" ? 4 : 2, d, max_nodes);
+  return {c.R, c.G, c.PH, c.nodes_lds};
+}
+
 // threads per block of the heap instantiation these shapes run (256, or 512
 // where a 512-row tile is walked one row per thread), 0 off the heap route
 int64_t score_heap_block(const std::string& dtype, int64_t d,
@@ -1014,7 +1099,7 @@ torch::Tensor score_forest(torch::Tensor X, torch::Tensor nodes_packed,
                            torch::Tensor ncount, int64_t num_trees,
                            int64_t height_limit, double c_norm,
                            bool finalize,
-                           c10::optional<torch::Tensor> heap) {
+                           c10::optional<torch::Tensor> heap, bool rowtile) {
   CHECK_CUDA(X);
   CHECK_CUDA(nodes_packed);
   CHECK_CONTIG(nodes_packed);
@@ -1035,6 +1120,34 @@ torch::Tensor score_forest(torch::Tensor X, torch::Tensor nodes_packed,
   const ifa::RowDtype dt = row_dtype(X);
   const ScoreCfg cfg = pick_score_cfg(ifa::row_elem_bytes(dt), d, max_nodes,
                                       height_limit);
+  if (cfg.rowtile && rowtile) {
+    const torch::Tensor nc = ncount.contiguous();
+    TORCH_CHECK(nc.scalar_type() == torch::kInt32 && nc.dim() == 1 &&
+                    nc.size(0) == Tpad,
+                "ncount must be int32 [Tpad]");
+    TORCH_CHECK(height_limit >= 0 && height_limit <= 64, "bad height");
+    const RowtileCfg rc =
+        pick_rowtile_cfg(ifa::row_elem_bytes(dt), d, max_nodes);
+    // IFA_ROWTILE_MAX_BLOCKS=<n> lowers the grid limit so that tests reach
+    // the grid-stride loop at small N
+    int64_t max_blocks = 8192;
+    if (const char* e = getenv("IFA_ROWTILE_MAX_BLOCKS")) {
+      const int64_t v = atoll(e);
+      if (v >= 1) max_blocks = std::min<int64_t>(v, 8192);
+    }
+    const int blocks =
+        (int)std::min<int64_t>((N + rc.R - 1) / rc.R, max_blocks);
+    const hipError_t err = ifa::launch_score_forest_rowtile(
+        dt, rc.G, rc.nodes_lds, X.data_ptr(), xl.rs, xl.cs,
+        nodes_packed.data_ptr<int32_t>(), nc.data_ptr<int32_t>(),
+        out.data_ptr<float>(), N, (int32_t)d, (int32_t)rc.SW, (int32_t)Tpad,
+        (int32_t)max_nodes, (int32_t)height_limit, (int32_t)rc.PH,
+        (float)num_trees, (float)c_norm, finalize ? 1 : 0, rc.lds, blocks,
+        current_stream());
+    TORCH_CHECK(err == hipSuccess, "score_forest_rowtile launch failed (G = ",
+                rc.G, ", ", rc.lds, " B of LDS): ", hipGetErrorString(err));
+    return out;
+  }
   if (cfg.heap && heap.has_value()) {
     const torch::Tensor& hp = *heap;
     CHECK_CUDA(hp);
@@ -2805,7 +2918,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("score_forest", &score_forest, "batched path-length scoring (K6)",
         py::arg("X"), py::arg("nodes_packed"), py::arg("ncount"),
         py::arg("num_trees"), py::arg("height_limit"), py::arg("c_norm"),
-        py::arg("finalize"), py::arg("heap") = py::none());
+        py::arg("finalize"), py::arg("heap") = py::none(),
+        py::arg("rowtile") = true);
+  m.def("score_rowtile_cfg", &score_rowtile_cfg,
+        "(rows per block, lanes per row, trees per barrier phase, records in "
+        "LDS) of the rowtile walk for (dtype, d, max_nodes, height)",
+        py::arg("dtype"), py::arg("d"), py::arg("max_nodes"),
+        py::arg("height"));
   m.def("score_extended_forest", &score_extended_forest,
         "batched EIF scoring (K7)");
   m.def("score_extended_sparse_v2", &score_extended_sparse_v2,

@@ -26,6 +26,7 @@ ext = CUDAExtension(
         "isolation_forest_amd/ops/hip/deep_kernels.hip",
         "isolation_forest_amd/ops/hip/explain_kernels.hip",
         "isolation_forest_amd/ops/hip/csr_kernels.hip",
+        "isolation_forest_amd/ops/hip/rowtile_kernels.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
